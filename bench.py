@@ -28,10 +28,22 @@ operands, inputs already resident in HBM:
             prefill of ONE sequence holding the 8 frames' visual tokens (64 text + 8 x 1152 = 9280 positions; 32 attention
             sub-layers) replicated on every rank -- the language model is not sharded on this path.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, runs W warm-up steps, times exactly K steps and prints ONE JSON line (rank 0) with the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...) and the configuration.  Everything else is measured only with
+--full, which adds to the same line
+  ms_per_step_repeats : the K-step region timed twice more, back to back;
+  box          : clocks / power / temperature of the GPU per phase of the run;
+  strong       : (default config, N > 1) the same 40 crops block-partitioned over the ranks, timed in the same run;
   roofline     : the dominant kernel of the step, algorithmic FLOPs / live HIP-event duration, against the dense bf16 MFMA peak;
+  path_mfma    : the step's algorithmic rate, against the peak and against this box's bare MFMA stream measured in the run;
+  fp16         : (N == 1, config 2) the same step with fp16 MFMA operands;
   cpu_baseline : the CPU oracle (oracle/slime_oracle.py, a restatement validated against the reference) timed on this box's
-                 host cores on a bounded sample (N == 1, config 2 only).
+                 host cores on a bounded sample (N == 1, config 2 only; --no-cpu-baseline drops it), and `parity` beside it.
+
+--dump-outputs DIR  after the timed steps, writes what the timed path returned in its last step (rank 0's visual tokens, or the
+                    prefill's hidden states for configs 4 / 5) as DIR/<name>.npy in float32; an output above 48 MB is written as a
+                    fixed, seeded sample of its rows (the line's `dumped` object says which).  Inputs and weights are seeded, so two
+                    builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -80,6 +92,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: repeats, clocks / power, the strong leg of N > 1, roofline probes, "
+                         "MFMA calibration, the fp16 leg, the CPU baseline and parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="run gather + adapter of a step on the tower's stream instead of a second stream")
@@ -476,6 +493,43 @@ class DeadlineGuard:
         return False
 
 
+class NoBox:
+    """Stands in for BoxSampler in a plain run (no --full): no telemetry source is opened and no thread samples."""
+
+    def mark(self, phase):
+        pass
+
+
+DUMP_MAX_BYTES = 48 << 20              # per output; a larger one is dumped as a seeded sample of its rows
+DUMP_SEED = 0
+
+
+def sample_output(t):
+    """Host float32 copy of one output of the timed path, taken right after the timed steps: the whole tensor, or -- above
+    DUMP_MAX_BYTES -- a fixed, seeded, sorted sample of its rows (the tensor viewed as [rows, last dim]).  Returns (array, info)."""
+    full_shape = list(t.shape)
+    flat = t.reshape(-1, t.shape[-1])
+    if flat.numel() * 4 <= DUMP_MAX_BYTES:
+        return t.float().cpu().numpy(), {"shape": full_shape, "sampled_rows": None}
+    keep = DUMP_MAX_BYTES // (flat.shape[1] * 4)
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    rows = torch.randperm(flat.shape[0], generator=g)[:keep].sort().values
+    arr = flat.index_select(0, rows.to(t.device)).float().cpu().numpy()
+    return arr, {"shape": full_shape, "sampled_rows": int(keep), "of_rows": int(flat.shape[0]), "row_seed": DUMP_SEED,
+                 "sample": "rows of the output viewed as [rows, last dim], torch.randperm(rows, seed) truncated and sorted"}
+
+
+def write_outputs(directory, arrays):
+    """DIR/<name>.npy for every (name, float32 array); returns the `dumped` object of the line."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    out = {}
+    for name, (arr, info) in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+        out[name] = {**info, "dumped_shape": list(arr.shape), "dtype": "float32"}
+    return out
+
+
 def self_launch(n):
     """`python bench.py --gpus N` with N > 1 and no rank environment: start the N ranks here (one process per GPU under
     torch.distributed.run, rendezvous on 127.0.0.1 and a free port -- the container hostname may not resolve) and hand the
@@ -565,7 +619,8 @@ def main():
     n_step = IMAGES * CPI                                # crops per step per GPU (config 2/4) or in total (config 3)
     strong = C["scaling"] == "strong"
     extra_cfg = {}
-    box = BoxSampler(local_rank)                         # clocks / power / temperature of this rank's GPU, sampled from here on
+    # --full: clocks / power / temperature of this rank's GPU, sampled from here on
+    box = BoxSampler(local_rank) if args.full else NoBox()
     box.mark("setup")
 
     # Steps are independent batches, so the tail of step i (all-gather + adapter: small, partly under-filled launches,
@@ -692,6 +747,8 @@ def main():
         box.mark("between")
         if out is not None:
             assert torch.isfinite(out.float()).all()
+            if phase == "timed" and args.dump_outputs:           # host copy now: the prefill's output buffers are reused by later steps
+                last_outputs["hidden_states" if prefill else "tokens"] = sample_output(out)
         return dt_s
 
     def max_over_ranks(sec):
@@ -703,20 +760,23 @@ def main():
         dist.all_gather(every, t)                            # each rank's own clock around the same K steps
         return max(float(e.item()) for e in every), [float(e.item()) for e in every]
 
-    box.mark("idle")
-    time.sleep(0.15)                                         # a few samples of the idle chip (context up, weights resident, nothing running)
+    last_outputs = {}                                        # --dump-outputs: name -> (host float32 array, info), from the headline region
+    if args.full:
+        box.mark("idle")
+        time.sleep(0.15)                                     # a few samples of the idle chip (context up, weights resident, nothing running)
     elapsed, every = max_over_ranks(timed_region())          # THE headline: warm-up, then the first K steps
     rank_ms = [e / args.steps * 1e3 for e in every]
-    # the same K steps twice more, back to back, no warm-up (the chip is warm): run-to-run spread inside one process on one box
-    repeats_s = [elapsed] + [max_over_ranks(timed_region(warmup=0, phase="repeat"))[0] for _ in range(REPEATS - 1)]
+    # --full: the same K steps twice more, back to back, no warm-up (the chip is warm): run-to-run spread inside one process on one box
+    repeats_s = [elapsed] + [max_over_ranks(timed_region(warmup=0, phase="repeat"))[0] for _ in range(REPEATS - 1)] if args.full else None
     box_ranks = None
     if collective:
-        # every rank's clocks / power inside the headline region (a rank on a throttled GPU is the one the MAX over ranks reports)
-        mine = box.phase_stats("timed")
-        t = torch.tensor([mine.get(k, {}).get("mean", float("nan")) for k in ("sclk_mhz", "power_w", "temp_c")], device=dev, dtype=torch.float64)
-        allb = [torch.zeros_like(t) for _ in range(world)]
-        dist.all_gather(allb, t)
-        box_ranks = [{k: (None if v != v else round(v, 1)) for k, v in zip(("sclk_mhz", "power_w", "temp_c"), x.tolist())} for x in allb]
+        if args.full:
+            # every rank's clocks / power inside the headline region (a rank on a throttled GPU is the one the MAX over ranks reports)
+            mine = box.phase_stats("timed")
+            t = torch.tensor([mine.get(k, {}).get("mean", float("nan")) for k in ("sclk_mhz", "power_w", "temp_c")], device=dev, dtype=torch.float64)
+            allb = [torch.zeros_like(t) for _ in range(world)]
+            dist.all_gather(allb, t)
+            box_ranks = [{k: (None if v != v else round(v, 1)) for k, v in zip(("sclk_mhz", "power_w", "temp_c"), x.tolist())} for x in allb]
         # what the communicator itself says (not the environment): backend name and the number of ranks in it
         extra_cfg["collective_backend"] = dist.get_backend()
         extra_cfg["rccl_ranks"] = dist.get_world_size() if dist.get_backend() == "nccl" else None
@@ -748,7 +808,7 @@ def main():
                        3: "image-crops/sec (ViT+projector) at 336px, 1+16 grid"}.get(args.config, "image-crops/sec (ViT+projector) at 336px, 1+4 grid"),
             "value": round(crops_total / elapsed, 1), "unit": "crops/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3), "ms_per_step_rank_min": round(min(rank_ms), 3), "ms_per_step_rank_max": round(max(rank_ms), 3),
-            "ms_per_step_repeats": [round(r / args.steps * 1e3, 3) for r in repeats_s],
+            **({"ms_per_step_repeats": [round(r / args.steps * 1e3, 3) for r in repeats_s]} if repeats_s else {}),
             "higher_is_better": True, "scaling": C["scaling"], "vs_baseline": None,
             "dtype": "bf16", "data": "synthetic"}
 
@@ -767,7 +827,7 @@ def main():
         print(json.dumps(res), flush=True)
 
     strong_obj = None
-    if collective and args.config == 2 and not strong:
+    if collective and args.config == 2 and not strong and args.full:
         guard = DeadlineGuard(float(os.environ.get("SLIME_BENCH_STRONG_DEADLINE_S", "240")), strong_leg_timed_out)
         try:
             with guard:
@@ -778,28 +838,11 @@ def main():
             time.sleep(3600)                                 # is printing the headline and ends this process: stay out of its way
 
     if rank == 0:
-        box.mark("probe")
-        step_gf = n_step * GF_VIT_PER_CROP + IMAGES * GF_GLOBAL_PER_IMAGE + IMAGES * LOCAL * GF_LOCAL_PER_CROP
-        if prefill:
-            step_gf += prefill.gflop
-        step_gf_reference = step_gf + IMAGES * (GF_GLOBAL_PER_IMAGE_REFERENCE - GF_GLOBAL_PER_IMAGE)
-        path_tflops = step_gf * (1 if strong else world) / (elapsed / args.steps) / 1e3
         halves = 2 if tower.vision_tower.two_streams else 1
         per_rank = -(-n_step // world) if strong else n_step
-        n_half = (per_rank + 1) // halves if per_rank >= 8 else per_rank          # encode() splits from 8 crops on
-        dom, per = kernel_roofline(tower.vision_tower, pixels[:n_half].contiguous())
-        roof_kernel = per[dom]
-        if prefill:
-            pk = prefill.kernel_times()
-            per.update(pk)
-            roof_kernel = pk["prefill_attention"]
-        # the driver's line (config 2, 40 crops per GPU) must carry a traffic figure; other launch shapes carry one if profiled
-        calib = mfma_stream_calibration(dev, dt, box)
-        traffic, traffic_src, traffic_head, traffic_err = pmc_traffic(roof_kernel["rocprof_name"], profiled_shape=(args.config == 2 and not strong and world == 1))
-        workload = WORKLOADS[args.config]
         res = {
             **headline_fields(),
-            "config": {"workload": workload, "baseline_config": args.config,
+            "config": {"workload": WORKLOADS[args.config], "baseline_config": args.config,
                        "crops_per_gpu": per_rank, "images_per_step": IMAGES * (1 if strong else world), "grid": f"1+{LOCAL}",
                        "parallelism": f"crop-parallel dp{world}" + (" + all-gather of tower features" if world > 1 else ""),
                        "tower_streams": halves,
@@ -811,66 +854,87 @@ def main():
                                             "row_major_copies_kept": ops.keep_row_major()},
                        "step_pipelining": "none" if tail_stream is None else "gather+adapter of step i on a second stream, under the tower of step i+1",
                        **extra_cfg},
-            "path_mfma": {"algorithmic_tflops": round(path_tflops, 1), "frac_of_peak": round(path_tflops / (PEAK_BF16_TFLOPS * world), 4),
-                          "gflop_per_step": round(step_gf, 1),
-                          "gflop_per_step_reference_arithmetic": round(step_gf_reference, 1),
-                          "gflop_note": "rates are priced on the EXECUTED arithmetic: the gated block's second Linear runs once per global token after the gate "
-                                        "mixed the hidden rows (linear map, gates sum to 1/(1+1e-6)); the reference's two complete experts would be the larger figure",
-                          # THIS box's bare MFMA stream, measured in this run right after the timed regions (no constant from another box)
-                          "power_capped_mfma_stream_tflops": calib["tflops"],
-                          "frac_of_power_capped_mfma_stream": round(path_tflops / (calib["tflops"] * world), 4),
-                          "mfma_stream_calibration": calib},
-            "roofline": {"bound": "mfma",
-                         "kernel": f"{roof_kernel['rocprof_name']} ({roof_kernel['label']}, M={roof_kernel['M']} N={roof_kernel['N']} K={roof_kernel['K']})",
-                         "achieved": roof_kernel["tflops"], "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(roof_kernel["tflops"] / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src, "traffic_head": traffic_head,
-                         # do the committed PMC passes describe the kernel sources this library was built from?
-                         "traffic_current": pmc_profile_is_current(),
-                         **({"traffic_error": traffic_err} if traffic_err else {}),
-                         "traffic_algorithmic": roof_kernel.get("algorithmic_bytes"),
-                         "launch_ms": roof_kernel["ms"], "launch_ms_min": roof_kernel["min_ms"], "launch_ms_max": roof_kernel.get("max_ms"),
-                         "frac_min": round(roof_kernel["gflop_per_launch"] / roof_kernel.get("max_ms", roof_kernel["ms"]) / PEAK_BF16_TFLOPS, 4),
-                         "frac_max": round(roof_kernel["gflop_per_launch"] / roof_kernel["min_ms"] / PEAK_BF16_TFLOPS, 4),
-                         "gflop_per_launch": roof_kernel["gflop_per_launch"],
-                         "method": "HIP events recorded by the tower driver (slime_vit_forward_ex probe) around this kernel on its launching "
-                                   "stream, once per layer over all 23 layers of a tower pass over one half batch (the step's launch shape), other "
-                                   "stream idle; achieved / frac = mean over the 23 launches, frac_min / frac_max from the slowest / fastest"
-                                   + ("; prefill kernels: HIP events around single launches at the step's shapes" if prefill else ""),
-                         "kernels": {v["label"]: {k: v[k] for k in ("rocprof_name", "ms", "min_ms", "max_ms", "tflops") if k in v} for v in per.values()}},
         }
         if prefill:
             res["config"].update(prefill.describe())
-        if strong_obj is not None:
-            res["strong"] = strong_obj
-        if world == 1 and args.config == 2 and not strong:
-            # The SAME step in the reference's inference dtype (fp16: llava/model/builder.py:43) -- the dtype whose projector
-            # outputs meet north_star's 1e-3 (parity.fp16 below): same region, same K / W, timed right after the bf16 line.
-            f16 = torch.float16
-            # a second encoder loaded from the fp32 state dicts (NOT the bf16 module cast to fp16 and back: lossy outside fp16's range)
-            enc16 = SlimeVisualEncoder(default_slime_config("synthetic:1234"))
-            enc16.load_visual_state(tower_sd, adapter_sd)
-            enc16.to(dev)
-            enc16.get_vision_tower().vision_tower.to(f16)
-            tower16, model16 = enc16.get_vision_tower(), enc16.get_model()
-            cur.update(pixels=pixels.to(f16), pg=model16.mm_projector.packed(f16), post=model16.sampler.post_qformer.packed(576, f16), dt=f16,
-                       tower=tower16)
-            e16 = timed_region(phase="fp16")
-            res["fp16"] = {"ms_per_step": round(e16 / args.steps * 1e3, 3), "value": round(n_step * args.steps / e16, 1), "unit": "crops/s",
-                           "vs_bf16": round(elapsed / e16, 4),
-                           "note": "same step, same timed region, fp16 MFMA operands (the reference's inference dtype; meets the 1e-3 target, see parity.fp16)"}
-            cur.update(pixels=pixels, pg=pg, post=post, dt=dt, tower=tower)
-            del enc16, tower16, model16
-        if world == 1 and args.config == 2 and not args.no_cpu_baseline:
-            res["cpu_baseline"], px_s, ref_s = cpu_baseline(tower_sd, adapter_sd, CPI)
-            res["parity"] = parity_vs_oracle(tower_sd, adapter_sd, px_s, ref_s, dev, NW, NH)
-        box.mark("after")
-        time.sleep(0.1)
-        box.stop()
-        res["box"] = {"device": D.device_label(dev), "cus": torch.cuda.get_device_properties(dev).multi_processor_count,
-                      **box.summary(("idle", "warmup", "timed", "repeat", "strong", "probe", "calibration", "fp16", "after")),
-                      **({"ranks_timed": box_ranks} if box_ranks else {}),
-                      "what": "this rank's GPU while the bench ran: idle = context up, nothing running; timed = the headline K steps; repeat = the two repeats; "
-                              "probe = per-kernel HIP-event probing; calibration = the bare MFMA stream; after = the last 0.1 s"}
+        if args.dump_outputs:
+            res["dumped"] = write_outputs(args.dump_outputs, last_outputs)
+        if args.full:
+            box.mark("probe")
+            step_gf = n_step * GF_VIT_PER_CROP + IMAGES * GF_GLOBAL_PER_IMAGE + IMAGES * LOCAL * GF_LOCAL_PER_CROP
+            if prefill:
+                step_gf += prefill.gflop
+            step_gf_reference = step_gf + IMAGES * (GF_GLOBAL_PER_IMAGE_REFERENCE - GF_GLOBAL_PER_IMAGE)
+            path_tflops = step_gf * (1 if strong else world) / (elapsed / args.steps) / 1e3
+            n_half = (per_rank + 1) // halves if per_rank >= 8 else per_rank          # encode() splits from 8 crops on
+            dom, per = kernel_roofline(tower.vision_tower, pixels[:n_half].contiguous())
+            roof_kernel = per[dom]
+            if prefill:
+                pk = prefill.kernel_times()
+                per.update(pk)
+                roof_kernel = pk["prefill_attention"]
+            # the driver's line (config 2, 40 crops per GPU) must carry a traffic figure; other launch shapes carry one if profiled
+            calib = mfma_stream_calibration(dev, dt, box)
+            traffic, traffic_src, traffic_head, traffic_err = pmc_traffic(roof_kernel["rocprof_name"], profiled_shape=(args.config == 2 and not strong and world == 1))
+            res.update({
+                "path_mfma": {"algorithmic_tflops": round(path_tflops, 1), "frac_of_peak": round(path_tflops / (PEAK_BF16_TFLOPS * world), 4),
+                              "gflop_per_step": round(step_gf, 1),
+                              "gflop_per_step_reference_arithmetic": round(step_gf_reference, 1),
+                              "gflop_note": "rates are priced on the EXECUTED arithmetic: the gated block's second Linear runs once per global token after the gate "
+                                            "mixed the hidden rows (linear map, gates sum to 1/(1+1e-6)); the reference's two complete experts would be the larger figure",
+                              # THIS box's bare MFMA stream, measured in this run right after the timed regions (no constant from another box)
+                              "power_capped_mfma_stream_tflops": calib["tflops"],
+                              "frac_of_power_capped_mfma_stream": round(path_tflops / (calib["tflops"] * world), 4),
+                              "mfma_stream_calibration": calib},
+                "roofline": {"bound": "mfma",
+                             "kernel": f"{roof_kernel['rocprof_name']} ({roof_kernel['label']}, M={roof_kernel['M']} N={roof_kernel['N']} K={roof_kernel['K']})",
+                             "achieved": roof_kernel["tflops"], "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                             "frac": round(roof_kernel["tflops"] / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src, "traffic_head": traffic_head,
+                             # do the committed PMC passes describe the kernel sources this library was built from?
+                             "traffic_current": pmc_profile_is_current(),
+                             **({"traffic_error": traffic_err} if traffic_err else {}),
+                             "traffic_algorithmic": roof_kernel.get("algorithmic_bytes"),
+                             "launch_ms": roof_kernel["ms"], "launch_ms_min": roof_kernel["min_ms"], "launch_ms_max": roof_kernel.get("max_ms"),
+                             "frac_min": round(roof_kernel["gflop_per_launch"] / roof_kernel.get("max_ms", roof_kernel["ms"]) / PEAK_BF16_TFLOPS, 4),
+                             "frac_max": round(roof_kernel["gflop_per_launch"] / roof_kernel["min_ms"] / PEAK_BF16_TFLOPS, 4),
+                             "gflop_per_launch": roof_kernel["gflop_per_launch"],
+                             "method": "HIP events recorded by the tower driver (slime_vit_forward_ex probe) around this kernel on its launching "
+                                       "stream, once per layer over all 23 layers of a tower pass over one half batch (the step's launch shape), other "
+                                       "stream idle; achieved / frac = mean over the 23 launches, frac_min / frac_max from the slowest / fastest"
+                                       + ("; prefill kernels: HIP events around single launches at the step's shapes" if prefill else ""),
+                             "kernels": {v["label"]: {k: v[k] for k in ("rocprof_name", "ms", "min_ms", "max_ms", "tflops") if k in v} for v in per.values()}},
+            })
+            if strong_obj is not None:
+                res["strong"] = strong_obj
+            if world == 1 and args.config == 2 and not strong:
+                # The SAME step in the reference's inference dtype (fp16: llava/model/builder.py:43) -- the dtype whose projector
+                # outputs meet north_star's 1e-3 (parity.fp16 below): same region, same K / W, timed right after the bf16 line.
+                f16 = torch.float16
+                # a second encoder loaded from the fp32 state dicts (NOT the bf16 module cast to fp16 and back: lossy outside fp16's range)
+                enc16 = SlimeVisualEncoder(default_slime_config("synthetic:1234"))
+                enc16.load_visual_state(tower_sd, adapter_sd)
+                enc16.to(dev)
+                enc16.get_vision_tower().vision_tower.to(f16)
+                tower16, model16 = enc16.get_vision_tower(), enc16.get_model()
+                cur.update(pixels=pixels.to(f16), pg=model16.mm_projector.packed(f16), post=model16.sampler.post_qformer.packed(576, f16), dt=f16,
+                           tower=tower16)
+                e16 = timed_region(phase="fp16")
+                res["fp16"] = {"ms_per_step": round(e16 / args.steps * 1e3, 3), "value": round(n_step * args.steps / e16, 1), "unit": "crops/s",
+                               "vs_bf16": round(elapsed / e16, 4),
+                               "note": "same step, same timed region, fp16 MFMA operands (the reference's inference dtype; meets the 1e-3 target, see parity.fp16)"}
+                cur.update(pixels=pixels, pg=pg, post=post, dt=dt, tower=tower)
+                del enc16, tower16, model16
+            if world == 1 and args.config == 2 and not args.no_cpu_baseline:
+                res["cpu_baseline"], px_s, ref_s = cpu_baseline(tower_sd, adapter_sd, CPI)
+                res["parity"] = parity_vs_oracle(tower_sd, adapter_sd, px_s, ref_s, dev, NW, NH)
+            box.mark("after")
+            time.sleep(0.1)
+            box.stop()
+            res["box"] = {"device": D.device_label(dev), "cus": torch.cuda.get_device_properties(dev).multi_processor_count,
+                          **box.summary(("idle", "warmup", "timed", "repeat", "strong", "probe", "calibration", "fp16", "after")),
+                          **({"ranks_timed": box_ranks} if box_ranks else {}),
+                          "what": "this rank's GPU while the bench ran: idle = context up, nothing running; timed = the headline K steps; repeat = the two repeats; "
+                                  "probe = per-kernel HIP-event probing; calibration = the bare MFMA stream; after = the last 0.1 s"}
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)
         print(json.dumps(res), flush=True)

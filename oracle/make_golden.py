@@ -36,6 +36,7 @@ REF = "/root/reference"
 sys.path.insert(0, REPO)
 
 from slime_amd import weights as W          # noqa: E402  (seeded generators; no compute)
+from oracle import golden_parts  # noqa: E402
 
 OUT = os.path.join(REPO, "tests", "golden")
 
@@ -236,7 +237,7 @@ def main():
         g[f"expert{lg}"] = p2(feats[0]).numpy()[::7, ::5]
     g["hidden_states_len"] = np.array([hs_count], dtype=np.int64)
     g["abs_pos_12_to_24"] = ref_get_abs_pos(asd["sampler.post_qformer.pos_embed"], (24, 24)).float().numpy()[::5, ::3]
-    np.savez(os.path.join(OUT, "tiny_stages.npz"), **g)
+    golden_parts.save(OUT, "tiny_stages", g)        # parts of at most ~1 MB each
     print("tiny_stages: done, hidden_states len", hs_count)
 
     # ------------------------------------------------------------------ (4) full ViT-L dims, sub-sampled

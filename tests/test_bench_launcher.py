@@ -147,3 +147,33 @@ else:
     assert r.returncode == 0 and json.loads(r.stdout.strip()) == {"fired": False}
     r = subprocess.run([sys.executable, "-c", code, os.path.join(ROOT, "bench.py"), "raise"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and json.loads(r.stdout.strip()) == {"fired": False, "raised": True}
+
+
+def test_parse_full_and_dump_outputs_are_opt_in(monkeypatch):
+    bench = _load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 5 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_whole_or_seeded_row_sample(monkeypatch, tmp_path):
+    """--dump-outputs: an output under the per-output cap is written whole; a larger one as the same sorted, seeded row sample every
+    run, so that two builds' files line up row for row."""
+    import numpy as np
+    import torch
+    bench = _load_bench()
+    small = torch.randn(2, 5, 8, dtype=torch.bfloat16)
+    arr, info = bench.sample_output(small)
+    assert arr.dtype == np.float32 and arr.shape == (2, 5, 8) and np.array_equal(arr, small.float().numpy()) and info["sampled_rows"] is None
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 4 * 6)                  # room for 6 rows of 8 floats
+    big = torch.arange(40 * 8, dtype=torch.float32).view(4, 10, 8)
+    a1, i1 = bench.sample_output(big)
+    a2, _ = bench.sample_output(big.clone())
+    assert a1.shape == (6, 8) and np.array_equal(a1, a2) and i1["sampled_rows"] == 6 and i1["of_rows"] == 40 and i1["shape"] == [4, 10, 8]
+    rows = a1[:, 0] / 8
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a1, big.view(40, 8).numpy()[rows.astype(int)])
+    dumped = bench.write_outputs(str(tmp_path / "o"), {"tokens": (a1, i1)})
+    assert dumped["tokens"]["dumped_shape"] == [6, 8] and np.array_equal(np.load(tmp_path / "o" / "tokens.npy"), a1)

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_contract_line():
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "3"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "3", "--full"],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
@@ -77,7 +77,7 @@ def test_bench_gpus_2_launches_its_own_ranks():
     """`python bench.py --gpus 2 ...` exactly as the driver types it (no torch.distributed.run around it, no rank environment):
     the script starts its two ranks itself.  One GPU here, so both ranks sit on cuda:0 and the collective backend is gloo (RCCL
     refuses two ranks on one device) -- the numbers mean nothing, the launch / rendezvous / gather / max-reduce / rank-0 line do."""
-    d = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], ONE_GPU_REHEARSAL)
+    d = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"], ONE_GPU_REHEARSAL)
     assert d["n_gpus"] == 2 and d["steps"] == 3 and d["warmup"] == 1 and d["scaling"] == "weak"
     assert d["config"]["launched_by"] == "bench.py self-launch" and d["config"]["collective_backend"] == "gloo"
     assert d["config"]["rccl_ranks"] is None                      # gloo rehearsal: no RCCL communicator to report
@@ -99,7 +99,7 @@ def test_bench_gpus_2_strong_leg_deadline_keeps_the_headline():
     """A strong leg that overruns its deadline (here: a deadline no leg can meet) must not cost the weak headline: the two ranks
     leave with status 0 and rank 0's line carries the complete headline fields plus `strong: {"error": "timeout ..."}`
     (bench.DeadlineGuard; the leg has never run on a multi-GPU node, and it runs before the ONE line is printed)."""
-    d = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], {**ONE_GPU_REHEARSAL, "SLIME_BENCH_STRONG_DEADLINE_S": "0.001"})
+    d = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"], {**ONE_GPU_REHEARSAL, "SLIME_BENCH_STRONG_DEADLINE_S": "0.001"})
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["scaling"] == "weak" and d["unit"] == "crops/s" and d["dtype"] == "bf16"
     assert abs(d["value"] - 80 * 1e3 / d["ms_per_step"]) / d["value"] < 0.01 and len(d["ms_per_step_repeats"]) == 3
     assert "timeout" in d["strong"]["error"] and d["roofline"] is None and d["config"]["gather_consumed"] is False
@@ -118,7 +118,7 @@ def test_bench_refuses_more_gpus_than_the_node_has():
 def test_bench_other_configs_print_their_line(config, extra):
     """BASELINE configs 3 / 4 / 5 through bench.py, 2 steps each (and the strong-scaling ones once more as a self-launched 2-rank
     rehearsal on the one GPU): those modes are not what the driver runs, so nothing else would notice them rotting."""
-    d = _bench(["--config", str(config), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + extra, ONE_GPU_REHEARSAL if extra else None)
+    d = _bench(["--config", str(config), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"] + extra, ONE_GPU_REHEARSAL if extra else None)
     world = 2 if extra else 1
     assert d["n_gpus"] == world and d["steps"] == 2 and d["config"]["baseline_config"] == config
     assert d["scaling"] == {1: "weak", 3: "strong", 4: "weak", 5: "strong"}[config]
@@ -133,3 +133,21 @@ def test_bench_other_configs_print_their_line(config, extra):
         assert d["config"]["prefill_seq_len"] == {4: 1216, 5: 9280}[config] and d["config"]["llama_layers"] == 32
         assert "prefill32_kernel" in r["kernel"]
         assert d["path_mfma"]["gflop_per_step_reference_arithmetic"] > d["path_mfma"]["gflop_per_step"] > d["config"]["prefill_gflop_per_step"]
+
+
+def test_plain_bench_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times exactly K steps and prints the contract fields only: no repeats, probes, calibration, fp16 leg or
+    CPU baseline.  --dump-outputs writes the last timed step's visual tokens (float32; [8, 1152, 4096] is above the per-output cap,
+    so a seeded sample of its rows)."""
+    import numpy as np
+    out = tmp_path / "outputs"
+    d = _bench(["--gpus", "1", "--steps", "4", "--warmup", "1", "--dump-outputs", str(out)])
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["unit"] == "crops/s" and d["dtype"] == "bf16"
+    assert d["higher_is_better"] is True and d["ms_per_step"] > 0 and abs(d["value"] - 40 * 1e3 / d["ms_per_step"]) / d["value"] < 0.01
+    for k in ("ms_per_step_repeats", "roofline", "path_mfma", "fp16", "cpu_baseline", "parity", "box", "strong"):
+        assert k not in d, k
+    info = d["dumped"]["tokens"]
+    assert info["shape"] == [8, 1152, 4096] and info["of_rows"] == 8 * 1152 and info["dtype"] == "float32"
+    a = np.load(out / "tokens.npy")
+    assert a.dtype == np.float32 and list(a.shape) == info["dumped_shape"] == [info["sampled_rows"], 4096]
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20 and np.isfinite(a).all() and np.abs(a).max() > 0

@@ -11,6 +11,7 @@ import torch.nn as nn
 from PIL import Image
 
 from conftest import rel_l2
+from oracle import golden_parts
 
 pytestmark = pytest.mark.gpu
 TOL = {torch.float16: 1.2e-3, torch.bfloat16: 8e-3}
@@ -421,7 +422,7 @@ def test_router_matches_reference_goldens(dev):
     from conftest import GOLDEN
     from slime_amd import ops, weights as W
     from oracle import slime_oracle as O
-    g = np.load(os.path.join(GOLDEN, "tiny_stages.npz"))
+    g = golden_parts.load(GOLDEN, "tiny_stages")
     tsd = W.strip_tower_prefix(W.make_tower_state_dict(W.TINY, seed=11))
     asd = W.make_adapter_state_dict(W.ADAPTER_TINY, seed=12)
     for n_local, size in ((2, (336, 336)), (4, (672, 672)), (6, (1344, 1344))):

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, rel_l2
+from oracle import golden_parts
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +47,7 @@ def test_tiny_tower_vs_oracle_and_golden(dev, tiny_weights, dtype):
     pt = ops.pack_tower(tsd, W.TINY, dtype, dev)
     out, hidden = ops.tower_forward(pt, px.to(dev), out_dtype=torch.float32, want_hidden=True)
     ref = O.tower_forward(tsd, W.TINY, px)
-    g = np.load(os.path.join(GOLDEN, "tiny_stages.npz"))
+    g = golden_parts.load(GOLDEN, "tiny_stages")
     assert out.shape == (3, 576, 128)
     assert rel_l2(out.cpu(), ref) < TOL[dtype]
     assert rel_l2(out.cpu(), g["n2_tower"]) < TOL[dtype]                 # the reference's own output
@@ -82,7 +83,7 @@ def test_tiny_adapter_vs_oracle(dev, tiny_weights, dtype):
     for lg in (0, 1):
         e = ops.gated_forward(pg, x[:1], learnable_gated=lg)[0]
         assert rel_l2(e.cpu(), O.gated_block_forward(proj_sd, feats[0], A.num_heads, learnable_gated=lg)) < TOL[dtype]
-    g = np.load(os.path.join(GOLDEN, "tiny_stages.npz"))
+    g = golden_parts.load(GOLDEN, "tiny_stages")
     assert rel_l2(glob.cpu(), g["n2_global"]) < TOL[dtype] * 1.5          # golden used the reference's tower output
     assert rel_l2(comp.cpu(), g["n2_compressed"]) < TOL[dtype] * 1.5
 

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import slime_oracle as O
+from oracle import golden_parts, slime_oracle as O
 from slime_amd import weights as W
 from conftest import GOLDEN, rel_l2
 
@@ -15,7 +15,7 @@ TOL = 2e-5   # fp32 restatement vs fp32 reference (different op order / sdpa vs 
 
 @pytest.fixture(scope="module")
 def tiny():
-    g = np.load(os.path.join(GOLDEN, "tiny_stages.npz"))
+    g = golden_parts.load(GOLDEN, "tiny_stages")
     tsd = W.strip_tower_prefix(W.make_tower_state_dict(W.TINY, seed=11))
     asd = W.make_adapter_state_dict(W.ADAPTER_TINY, seed=12)
     return g, tsd, asd

@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from conftest import rel_l2
+from oracle import golden_parts
 
 REF = "/root/reference"
 pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "llava")), reason="the reference is only present in the build container")
@@ -181,7 +182,7 @@ def test_reference_glue_runs_unchanged_over_swapped_builders(swapped, tmp_path):
 
     # ---- encode_images (:212-269), sampler branch, on the goldens' crops; the router's text = the goldens' text rows, delivered
     # through embed_tokens + get_pure_text_embedding (:162-210) exactly as the reference delivers it
-    g = np.load(os.path.join(GOLD, "tiny_stages.npz"))
+    g = golden_parts.load(GOLD, "tiny_stages")
     mask9 = torch.tensor([1, 1, 1, 1, 1, 1, 0, 0, 1], dtype=torch.long)
     emb = model.embed_tokens
     with torch.no_grad():
@@ -275,6 +276,6 @@ def test_reference_glue_batch_branch_and_plain_projectors(swapped, tmp_path):
     m2 = _reference_model(A, cfg2, 64)
     m2.get_vision_tower().load_model()
     m2.get_model().mm_projector.load_state_dict(W.sub_state(asd, "mm_projector."))
-    g = np.load(os.path.join(GOLD, "tiny_stages.npz"))
+    g = golden_parts.load(GOLD, "tiny_stages")
     feats, _ = m2.encode_images(W.synthetic_pixels(2, seed=31), input_ids=ids, attention_mask=torch.ones_like(ids))
     assert rel_l2(feats[:, ::7, ::5], torch.from_numpy(g["batched_gated"])) < 5e-5
