@@ -17,7 +17,7 @@ import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# SLIME_HIP_LIBRARY: run against another build of the SAME ABI (tools/build_variants.sh A/B libraries); there is still no fallback --
+# SLIME_HIP_LIBRARY: run against another build of the SAME ABI (a product library built from another tree); there is still no fallback --
 # a missing file raises in load()
 LIB_PATH = os.environ.get("SLIME_HIP_LIBRARY") or os.path.join(_HERE, "libslime_hip.so")
 DIAG_LIB_PATH = os.path.join(_HERE, "libslime_hip_diag.so")

@@ -51,18 +51,12 @@ static bool is16(int dt) { return dt == SLIME_BF16 || dt == SLIME_F16; }
 // ------------------------------------------------------------------------------------------------
 // CLIP tower
 // ------------------------------------------------------------------------------------------------
-#ifndef SLIME_OPT_ALIAS_WS
-#define SLIME_OPT_ALIAS_WS 1
-#endif
 // Round 5: the residual stream between the layers is SPLIT (hi = T(h), which IS the next GEMM's operand, + a lower part) instead of
 // fp32 rows plus a separate T(h) copy; round 6 (ABI 7): the lower part is one signed byte per element (common.h resid_delta): the
-// out_proj / fc2 epilogues move 6 bytes per element -- 8 with a 16-bit lower part (round 5), 10 with the fp32 stream
-// (SLIME_EPI_BIAS_RESID_SPLIT_LN).  0 = the fp32 stream of rounds 1-4 (tools/build_variants.sh A/B).
-#ifndef SLIME_OPT_SPLIT_RESID
-#define SLIME_OPT_SPLIT_RESID 1
-#endif
+// out_proj / fc2 epilogues (SLIME_EPI_BIAS_RESID_SPLIT_LN) move 6 bytes per element -- 8 with a 16-bit lower part (round 5), 10 with
+// the fp32 stream of rounds 1-4.
 struct VitPlan {
-    size_t xn, qkv, ctx, ff, h, stats, total;   // offsets (h: the fp32 residual rows, or the lower part of the split stream: one byte per element since ABI 7)
+    size_t xn, qkv, ctx, ff, lo, stats, total;  // offsets (lo: the lower part of the split stream, one byte per element)
 };
 
 static VitPlan vit_plan(const slime_vit_desc* d, int n) {
@@ -71,10 +65,9 @@ static VitPlan vit_plan(const slime_vit_desc* d, int n) {
     VitPlan p{};
     size_t off = 0;
     auto take = [&](size_t b) { size_t o = align_up(off, 256); off = o + b; return o; };
-    p.h = take(M * D * (SLIME_OPT_SPLIT_RESID ? 1 : 4));
+    p.lo = take(M * D);
     p.xn = take(M * D * 2);
     const size_t ff_bytes = M * (size_t)d->inter * 2;
-#if SLIME_OPT_ALIAS_WS
     // q/k/v and the attention context die before fc1 writes the MLP's intermediate rows, and those die before the next layer's q/k/v
     // GEMM: the three share one region (for CLIP-L, 3 D + D = the intermediate width exactly).  The launches of a stream are serial, so
     // nothing else changes -- except that a 20-crop stream now cycles through 165 MB instead of 260, and the 256 MiB memory-side
@@ -84,11 +77,6 @@ static VitPlan vit_plan(const slime_vit_desc* d, int n) {
     p.ff = take(region);
     p.qkv = p.ff;
     p.ctx = p.ff + qkv_bytes;
-#else
-    p.qkv = take(M * 3 * D * 2);
-    p.ctx = take(M * D * 2);
-    p.ff = take(ff_bytes);
-#endif
     p.stats = take(M * (D / 64) * 2 * sizeof(float));      // LayerNorm fold: (sum, sum of squares) per row and 64-column group
     p.total = align_up(off, 256);
     return p;
@@ -117,9 +105,7 @@ static int vit_validate(const slime_vit_desc* d) {
 
 extern "C" int slime_vit_check(const slime_vit_desc* d) { return vit_validate(d); }
 
-extern "C" int slime_vit_residual_epilogue(void) {
-    return SLIME_OPT_SPLIT_RESID ? SLIME_EPI_BIAS_RESID_SPLIT_LN : SLIME_EPI_BIAS_RESID_F32_LN;
-}
+extern "C" int slime_vit_residual_epilogue(void) { return SLIME_EPI_BIAS_RESID_SPLIT_LN; }
 
 extern "C" size_t slime_vit_workspace_bytes(const slime_vit_desc* d, int n_crops) {
     if (!d || n_crops <= 0 || d->patch <= 0) return 0;
@@ -185,30 +171,17 @@ static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, i
     const int dt = d->dtype;
     float* stats = (float*)(w + p.stats);
     const int G = D / 64;
-#if SLIME_OPT_SPLIT_RESID
     // residual stream = (xn, lo): xn = T(h) is the upper part AND the operand of the q/k/v / fc1 GEMMs, lo = one signed byte per element (common.h resid_delta)
-    void* lo = w + p.h;
-    float* h = nullptr;
-#else
-    void* lo = nullptr;
-    float* h = hidden_f32 ? hidden_f32 : (float*)(w + p.h);
-#endif
+    void* lo = w + p.lo;
 
     // patch embed (MFMA conv), class token, position table, pre-LayerNorm and the first folded LN1's operand + partial sums: ONE launch
-    TRY(slime_patch_embed_prenorm(pixels, pix_dtype, d->patch_w_frag, d->cls, d->pos, d->pre_ln_w, d->pre_ln_b, d->eps, h, xn, lo, stats,
-                                  dt, n, d->image, d->patch, d->kpad, D, stream));
+    // (no fp32 rows: h = NULL)
+    TRY(slime_patch_embed_prenorm(pixels, pix_dtype, d->patch_w_frag, d->cls, d->pos, d->pre_ln_w, d->pre_ln_b, d->eps, nullptr, xn, lo,
+                                  stats, dt, n, d->image, d->patch, d->kpad, D, stream));
     // hidden_states[i] of HF's output_hidden_states=True (entry 0 = the pre-LayerNorm'd embeddings, entry i = after layer i):
-    // a device-side copy of the residual stream on the call's stream (capturable), one per state
-#if SLIME_OPT_SPLIT_RESID
-#define SNAPSHOT(idx) TRY(slime_gather_rows_split(xn, lo, dt, S, 0, states + (size_t)(idx) * M * D, SLIME_F32, n, S, D, stream))
-#else
-#define SNAPSHOT(idx)                                                                                                           \
-    do {                                                                                                                        \
-        if (hipMemcpyAsync(states + (size_t)(idx) * M * D, h, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice,         \
-                           (hipStream_t)stream) != hipSuccess) { slime_set_error("vit: hidden-state snapshot failed"); return SLIME_ELAUNCH; } \
-    } while (0)
-#endif
-    if (states) SNAPSHOT(0);
+    // the residual stream joined to fp32 on the call's stream (capturable), one per state
+    auto snapshot = [&](int idx) { return slime_gather_rows_split(xn, lo, dt, S, 0, states + (size_t)idx * M * D, SLIME_F32, n, S, D, stream); };
+    if (states) TRY(snapshot(0));
 
     // Layer loop, 5 launches per layer.  Both LayerNorms are FOLDED into the GEMMs around them (slime_gemm_ex): the GEMM that
     // updates the residual stream (previous fc2 / out_proj, or the embedding kernel) leaves the rows rounded to T (`xn`) and
@@ -218,7 +191,6 @@ static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, i
         auto layer_w = [&](const void* base, size_t per_layer) -> const void* {     // this layer's slice of a per-layer weight (or NULL)
             return base ? (const char*)base + (size_t)l * per_layer * 2 : nullptr;
         };
-        const bool last = l + 1 == d->layers_run;
         slime_gemm_args ga{};
         ga.M = M; ga.dtype = dt; ga.ln_eps = d->eps;
         // q/k/v = LN1(h) Wqkv^T + b  (HF :370-371, :309-311)
@@ -230,22 +202,16 @@ static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, i
         PROBED(2, slime_attention(qkv, (long)S * 3 * D, 3 * D, qkv + (size_t)D * 2, (long)S * 3 * D, 3 * D,
                                   qkv + (size_t)2 * D * 2, (long)S * 3 * D, 3 * D, ctx, (long)S * D, D, n, d->heads, 64, S, S,
                                   dt, stream));
-        // the two GEMMs that update the residual stream and prepare the next folded LayerNorm
-        auto resid_update = [&](slime_gemm_args& r, bool with_ln) {
-#if SLIME_OPT_SPLIT_RESID
-            (void)with_ln;                                   // the last layer's partial sums are written and never read
+        // the two GEMMs that update the residual stream and prepare the next folded LayerNorm (the last layer's partial sums are
+        // written and never read)
+        auto resid_update = [&](slime_gemm_args& r) {
             r.C = xn; r.ldc = D; r.lo8 = lo; r.ldlo = D; r.stats_out = stats; r.epilogue = SLIME_EPI_BIAS_RESID_SPLIT_LN;
-#else
-            r.C = h; r.ldc = D;
-            r.epilogue = with_ln ? SLIME_EPI_BIAS_RESID_F32_LN : SLIME_EPI_BIAS_RESID_F32;
-            if (with_ln) { r.x16 = xn; r.ldx = D; r.stats_out = stats; }
-#endif
         };
         // h += ctx Wo^T + b; leaves T(h) and its partial sums for LN2  (HF :372-377)
         ga = slime_gemm_args{};
         ga.M = M; ga.dtype = dt;
         ga.A = ctx; ga.lda = D; ga.B = layer_w(d->w_o, (size_t)D * D); ga.bias = d->b_o + (size_t)l * D; ga.N = D; ga.K = D;
-        resid_update(ga, true);
+        resid_update(ga);
         ga.B_frag = layer_w(d->w_o_frag, (size_t)D * D);
         PROBED(3, slime_gemm_ex(&ga, stream));
         // ff = quick_gelu(LN2(h) W1^T + b)  (HF :379-380, :346-350)
@@ -255,26 +221,20 @@ static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, i
         ga.epilogue = SLIME_EPI_BIAS_QUICKGELU_T; ga.ln_stats = stats; ga.ln_groups = G; ga.ln_colsum = d->colsum_fc1 + (size_t)l * F;
         ga.B_frag = layer_w(d->w_fc1_frag, (size_t)F * D);
         PROBED(5, slime_gemm_ex(&ga, stream));
-        // h += ff W2^T + b; prepares the next layer's LN1 unless this is the last layer that runs  (HF :381-383)
+        // h += ff W2^T + b; prepares the next layer's LN1  (HF :381-383)
         ga = slime_gemm_args{};
         ga.M = M; ga.dtype = dt;
         ga.A = ff; ga.lda = F; ga.B = layer_w(d->w_fc2, (size_t)D * F); ga.bias = d->b_fc2 + (size_t)l * D; ga.N = D; ga.K = F;
-        resid_update(ga, !last);
+        resid_update(ga);
         ga.B_frag = layer_w(d->w_fc2_frag, (size_t)D * F);
         PROBED(6, slime_gemm_ex(&ga, stream));
-        if (states) SNAPSHOT(l + 1);
+        if (states) TRY(snapshot(l + 1));
     }
-#if SLIME_OPT_SPLIT_RESID
     if (hidden_f32) TRY(slime_gather_rows_split(xn, lo, dt, S, 0, hidden_f32, SLIME_F32, n, S, D, stream));
     if (out) {
         // feature_select: 'patch' drops the class token (clip_encoder.py:38-39), cast to out dtype (:52,56)
         TRY(slime_gather_rows_split(xn, lo, dt, S, keep_cls ? 0 : 1, out, out_dtype, n, keep_cls ? S : P, D, stream));
     }
-#else
-    if (out) {
-        TRY(slime_gather_rows(h, S, keep_cls ? 0 : 1, out, out_dtype, n, keep_cls ? S : P, D, stream));
-    }
-#endif
     return SLIME_OK;
 }
 
@@ -473,9 +433,6 @@ extern "C" int slime_gated_forward(const slime_mlp_desc* mlp, const slime_resamp
 // ------------------------------------------------------------------------------------------------
 // Fused adapter (GatedBlock on the global crops + post_qformer/MLP/merge on the local crops)
 // ------------------------------------------------------------------------------------------------
-#ifndef SLIME_OPT_ADAPTER_DIRECT
-#define SLIME_OPT_ADAPTER_DIRECT 1      // 0 = round 4's fp32 rows + two merge_rows passes (tools/build_variants.sh A/B)
-#endif
 int adapter_row_map_launch(int* map, long rows_g, int P, long rows_l, long per_image_local, int g, int nw, int merge, long out_image_stride,
                            void* stream);                                   // rowwise.hip (internal)
 struct AdapterPlan { size_t xg32, xl32, stack, e, mlp, res, gates, rmap, total; long rows_g, rows_l, rows_all; int segs_g; };
@@ -573,7 +530,7 @@ extern "C" int slime_adapter_forward(const slime_mlp_desc* mlp, const slime_resa
     // passes (two launches, 151 MB written + read back per 8 x (1+4) step).  The same values, rounded once by the same RNE pack as the
     // merge kernel's: bit-identical to the per-module sequence.  Other output dtypes (a 16-bit type that is not the operand type) keep
     // the fp32 rows + merge path.
-    const bool direct = SLIME_OPT_ADAPTER_DIRECT && (out_dtype == SLIME_F32 || out_dtype == dt);
+    const bool direct = out_dtype == SLIME_F32 || out_dtype == dt;
     int* rmap = (int*)(w + p.rmap);
     if (direct) {
         SLIME_REQUIRE((long)n_images * out_image_stride < (1L << 31), "adapter: token buffer too large for the 32-bit row map");

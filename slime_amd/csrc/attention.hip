@@ -236,7 +236,7 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, char* smem, const i
                 for (int p = 0; p < DT / 2; ++p) {
                     float v[8] = {o[s][2 * p][0] * inv, o[s][2 * p][1] * inv, o[s][2 * p][2] * inv, o[s][2 * p][3] * inv,
                                   o[s][2 * p + 1][0] * inv, o[s][2 * p + 1][1] * inv, o[s][2 * p + 1][2] * inv, o[s][2 * p + 1][3] * inv};
-                    st_stream(reinterpret_cast<u32x4*>(obase + ((size_t)qr * a.o_rs + 32 * p + 8 * g) * 2), pack8<T>(v));
+                    *reinterpret_cast<u32x4*>(obase + ((size_t)qr * a.o_rs + 32 * p + 8 * g) * 2) = pack8<T>(v);
                 }
             }
         }
@@ -567,7 +567,7 @@ __device__ __forceinline__ void attn64_body(const AttnArgs& a, char* smem, const
                 for (int p = 0; p < DT / 2; ++p) {
                     float v[8] = {o[s][2 * p][0] * inv, o[s][2 * p][1] * inv, o[s][2 * p][2] * inv, o[s][2 * p][3] * inv,
                                   o[s][2 * p + 1][0] * inv, o[s][2 * p + 1][1] * inv, o[s][2 * p + 1][2] * inv, o[s][2 * p + 1][3] * inv};
-                    st_stream(reinterpret_cast<u32x4*>(obase + ((size_t)qr * a.o_rs + 32 * p + 8 * g) * 2), pack8<T>(v));
+                    *reinterpret_cast<u32x4*>(obase + ((size_t)qr * a.o_rs + 32 * p + 8 * g) * 2) = pack8<T>(v);
                 }
             }
         }
@@ -610,9 +610,6 @@ __global__ void __launch_bounds__(512) attn64_kernel(AttnArgs a) {
 // ================================================================================================
 // RING (rows, a power of two; 0 = the resident 608-row panel): K and V live in a ring of RING rows each -- granule gi sits in slot
 // gi mod (RING / 8 NW) -- so a workgroup needs 2 x RING x 128 bytes of LDS instead of 152 KiB (attn64g_kernel below).
-#ifndef SLIME_OPT_ATTN_SHORT_TAIL
-#define SLIME_OPT_ATTN_SHORT_TAIL 1
-#endif
 // VABL (diagnostic build, variant 40; WRONG results, right timing): the eight ds_read_b64_tr_b16 V^T reads of a kv step are replaced
 // by eight plain ds_read_b64 of the same step's 4 KiB at lane-linear addresses (64 lanes x 8 B = every bank exactly once per pass:
 // conflict free) -- the same number of LDS instructions, bytes and waits without the 2-way bank conflict.  The difference to the
@@ -901,10 +898,10 @@ __device__ __forceinline__ void attn64r_pass(const AttnArgs& a, char* smem, cons
 #endif
         constexpr std::false_type FULL_STEP{};
         constexpr std::true_type SHORT_STEP{};
-        // Ragged key range whose last step holds at most 16 live keys (CLIP: 577 = 18 x 32 + 1; round 5, SLIME_OPT_ATTN_SHORT_TAIL):
+        // Ragged key range whose last step holds at most 16 live keys (CLIP: 577 = 18 x 32 + 1; round 5):
         // that step is multiplied half-wide (one key tile, K = 16 MFMAs) instead of as a masked 32-key step.  The choice depends on
         // n_kv alone, never on the launch form, so the bit-invariance across forms and batch sizes holds.
-        const bool short_tail = SLIME_OPT_ATTN_SHORT_TAIL && !KPF && ragged && (a.n_kv & 31) <= 16 && steps >= 2;
+        const bool short_tail = !KPF && ragged && (a.n_kv & 31) <= 16 && steps >= 2;
         if constexpr (KPF) k_request();                      // step 0
         if (steps > 1) before_step(1);
         qk(sA, steps > 1, FULL_STEP);                        // multiplies step 0, requests step 1
@@ -941,22 +938,18 @@ __device__ __forceinline__ void attn64r_pass(const AttnArgs& a, char* smem, cons
                 for (int p = 0; p < DT / 2; ++p) {
                     float v[8] = {o[s][2 * p][0] * inv, o[s][2 * p][1] * inv, o[s][2 * p][2] * inv, o[s][2 * p][3] * inv,
                                   o[s][2 * p + 1][0] * inv, o[s][2 * p + 1][1] * inv, o[s][2 * p + 1][2] * inv, o[s][2 * p + 1][3] * inv};
-                    st_stream(reinterpret_cast<u32x4*>(obase + ((size_t)qr * a.o_rs + 32 * p + 8 * g) * 2), pack8<T>(v));
+                    *reinterpret_cast<u32x4*>(obase + ((size_t)qr * a.o_rs + 32 * p + 8 * g) * 2) = pack8<T>(v);
                 }
             }
         }
     }
 }
 
-#ifndef SLIME_OPT_ATTN_PAIR
-#define SLIME_OPT_ATTN_PAIR 1
-#endif
 template <typename T, int AHEAD = 3, int VABL = 0>
 __global__ void __launch_bounds__(512) attn64r_kernel(AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NW = 8, P1 = 3 * NW;                        // pass 1: <= 3 sub-blocks per wave
     int h = blockIdx.x, b = blockIdx.y, z = blockIdx.z;
-#if SLIME_OPT_ATTN_PAIR
     // Two workgroups share a (crop, head) when the query blocks are split: both stage the same K/V panel.  The launch order deals
     // workgroup L to XCD L & 7 (each XCD has its own L2), and in grid order the partners are heads x crops apart -- the second one
     // fetched the panel across the fabric again (117 MB read per launch against 71 MB of q/k/v, profiles/r04_pmc_kernels.json).
@@ -966,7 +959,6 @@ __global__ void __launch_bounds__(512) attn64r_kernel(AttnArgs a) {
         const int j = L >> 3, p = (j / (int)gridDim.z) * 8 + (L & 7);
         z = j % (int)gridDim.z; h = p % (int)gridDim.x; b = p / (int)gridDim.x;
     }
-#endif
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int total_sb = (a.n_q + 15) >> 4;
     const int wg_sb0 = z * a.sb_per_wg;

@@ -109,32 +109,6 @@ __device__ __forceinline__ u32x4 pack8(const float* v) {
     return r;
 }
 
-// Measured alternative (round 4, profiles/r04_fabric_traffic.txt), OFF: results leaving with the non-temporal hint (stream / evict
-// first) and read-once inputs (the fp32 residual rows) arriving with it, so that neither pushes the shared GEMM operand panels out of
-// an XCD's 4 MiB L2.  It does cut the fabric reads (fc1 199 -> 156 MB per launch together with the row ownership below) -- and the
-// 40-crop tower gets SLOWER, 14.9 -> 15.9 ms.  Not separated further; the candidates: a streamed result is not kept for its only
-// reader, the NEXT kernel, and the epilogue's 64-byte row segments leave as partial lines instead of being merged in L2 first.
-// `make` leaves it off; tools/build_variants.sh builds the A/B libraries.
-#ifndef SLIME_OPT_NT
-#define SLIME_OPT_NT 0
-#endif
-template <typename V>
-__device__ __forceinline__ void st_stream(V* p, const V v) {
-#if SLIME_OPT_NT
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-template <typename V>
-__device__ __forceinline__ V ld_stream(const V* p) {
-#if SLIME_OPT_NT
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
-
 // ---- the residual stream's lower part (ABI 7): ONE SIGNED BYTE per element -------------------------------------------------------
 // The stream is kept as hi = T(h) (RNE: hi IS the next GEMM's operand) and d8 = the next 8 bits of h's fp32 pattern, stored as the
 // signed distance of h's pattern from hi's in units of 2^SH (SH = 8 for bf16, 5 for fp16), rounded DOWN, and read back at the

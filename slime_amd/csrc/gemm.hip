@@ -114,6 +114,8 @@ template <int EPI> struct EpiOutIsT { static constexpr bool value = (EPI <= SLIM
 //   * the bias is loaded once up front; results are formed in place in the accumulators (distinct
 //     registers per store) and stored back to back;
 //   * the fp32 residual is fetched in register double-buffered batches, one batch ahead of the stores.
+// Loads and stores are plain: with the non-temporal hint the 40-crop tower got slower, 14.9 -> 15.9 ms (round 4,
+// profiles/r04_fabric_traffic.txt).
 // LN (consumer side of the LayerNorm fold): lnrow points at this lane's first row of the workgroup's (rstd, -mu rstd) table.
 template <typename T, int EPI, int MI, int NI, bool FULL, bool LN = false>
 __device__ __forceinline__ void epilogue_wave(const GemmArgs& g, f32x4 (&acc)[MI][NI], const int row_base, const int col_base,
@@ -179,7 +181,7 @@ __device__ __forceinline__ void epilogue_wave(const GemmArgs& g, f32x4 (&acc)[MI
                 }
                 const u32x4 w = pack8<T>(v);
                 if (in_range(row))
-                    st_stream(reinterpret_cast<u32x4*>(reinterpret_cast<char*>(g.C) + ((size_t)row * g.ldc + col_base + 32 * p) * 2), w);
+                    *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(g.C) + ((size_t)row * g.ldc + col_base + 32 * p) * 2) = w;
             }
         }
         return;
@@ -198,8 +200,8 @@ __device__ __forceinline__ void epilogue_wave(const GemmArgs& g, f32x4 (&acc)[MI
 #pragma unroll
                 for (int p = 0; p < NP; ++p) {
                     const float* src = C + (size_t)row * g.ldc + col_base + 32 * p;
-                    hb[buf][ii][p][0] = ld_stream(reinterpret_cast<const f32x4*>(src));
-                    hb[buf][ii][p][1] = ld_stream(reinterpret_cast<const f32x4*>(src + 4));
+                    hb[buf][ii][p][0] = *reinterpret_cast<const f32x4*>(src);
+                    hb[buf][ii][p][1] = *reinterpret_cast<const f32x4*>(src + 4);
                 }
             }
         };
@@ -220,8 +222,8 @@ __device__ __forceinline__ void epilogue_wave(const GemmArgs& g, f32x4 (&acc)[MI
                     acc[i][2 * p + 1][2] += bias[p][6] + h1[2]; acc[i][2 * p + 1][3] += bias[p][7] + h1[3];
                     if (in_range(row)) {
                         float* o = C + (size_t)row * g.ldc + col_base + 32 * p;
-                        st_stream(reinterpret_cast<f32x4*>(o), acc[i][2 * p]);
-                        st_stream(reinterpret_cast<f32x4*>(o + 4), acc[i][2 * p + 1]);
+                        *reinterpret_cast<f32x4*>(o) = acc[i][2 * p];
+                        *reinterpret_cast<f32x4*>(o + 4) = acc[i][2 * p + 1];
                     }
                 }
                 if constexpr (EPI == SLIME_EPI_BIAS_RESID_F32_LN) {
@@ -237,7 +239,7 @@ __device__ __forceinline__ void epilogue_wave(const GemmArgs& g, f32x4 (&acc)[MI
                             w[0] = T::pack2(acc[i][2 * p][0], acc[i][2 * p][1]); w[1] = T::pack2(acc[i][2 * p][2], acc[i][2 * p][3]);
                             w[2] = T::pack2(acc[i][2 * p + 1][0], acc[i][2 * p + 1][1]); w[3] = T::pack2(acc[i][2 * p + 1][2], acc[i][2 * p + 1][3]);
                             if (in_range(row))
-                                st_stream(reinterpret_cast<u32x4*>(g.x16 + ((size_t)row * g.ldx + col_base + 32 * p) * 2), w);
+                                *reinterpret_cast<u32x4*>(g.x16 + ((size_t)row * g.ldx + col_base + 32 * p) * 2) = w;
                             // sums of the fp32 values (the rounded ones differ by 2^-9 relative per element with random sign:
                             // far below what the statistics need, and unpacking them again would double this loop's VALU work)
 #pragma unroll
@@ -275,8 +277,8 @@ __device__ __forceinline__ void epilogue_wave(const GemmArgs& g, f32x4 (&acc)[MI
             if constexpr (!FULL) row = min(row, g.M - 1);
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
-                rh[buf][p] = ld_stream(reinterpret_cast<const u32x4*>(Hi + ((size_t)row * g.ldc + col_base + 32 * p) * 2));
-                rl[buf][p] = ld_stream(reinterpret_cast<const u32x2*>(Lo + ((size_t)row * g.ldlo + col_base + 32 * p)));
+                rh[buf][p] = *reinterpret_cast<const u32x4*>(Hi + ((size_t)row * g.ldc + col_base + 32 * p) * 2);
+                rl[buf][p] = *reinterpret_cast<const u32x2*>(Lo + ((size_t)row * g.ldlo + col_base + 32 * p));
             }
         };
         load_step(0, 0);
@@ -307,9 +309,9 @@ __device__ __forceinline__ void epilogue_wave(const GemmArgs& g, f32x4 (&acc)[MI
                         nd[2 * e + 1] = resid_delta<T>(c1, T::hi(w[e]));
                     }
                     if (in_range(row)) {
-                        st_stream(reinterpret_cast<u32x4*>(Hi + ((size_t)row * g.ldc + col_base + 32 * p) * 2), w);
-                        st_stream(reinterpret_cast<u32x2*>(Lo + ((size_t)row * g.ldlo + col_base + 32 * p)),
-                                  u32x2{pack_bytes(nd[0], nd[1], nd[2], nd[3]), pack_bytes(nd[4], nd[5], nd[6], nd[7])});
+                        *reinterpret_cast<u32x4*>(Hi + ((size_t)row * g.ldc + col_base + 32 * p) * 2) = w;
+                        *reinterpret_cast<u32x2*>(Lo + ((size_t)row * g.ldlo + col_base + 32 * p)) =
+                            u32x2{pack_bytes(nd[0], nd[1], nd[2], nd[3]), pack_bytes(nd[4], nd[5], nd[6], nd[7])};
                     }
                     // partial sums in the element order of BIAS_RESID_F32_LN
 #pragma unroll
@@ -338,7 +340,7 @@ __device__ __forceinline__ void epilogue_wave(const GemmArgs& g, f32x4 (&acc)[MI
                 if constexpr (!FULL) row = min(row, g.M - 1);
 #pragma unroll
                 for (int p = 0; p < NP; ++p)
-                    rb[buf][ii][p] = ld_stream(reinterpret_cast<const u32x4*>(g.resid + ((size_t)row * g.ldr + col_base + 32 * p) * 2));
+                    rb[buf][ii][p] = *reinterpret_cast<const u32x4*>(g.resid + ((size_t)row * g.ldr + col_base + 32 * p) * 2);
             }
         };
         load_batch(0, 0);
@@ -359,7 +361,7 @@ __device__ __forceinline__ void epilogue_wave(const GemmArgs& g, f32x4 (&acc)[MI
                     v[6] = acc[i][2 * p + 1][2] + bias[p][6] + T::lo(r[3]); v[7] = acc[i][2 * p + 1][3] + bias[p][7] + T::hi(r[3]);
                     const u32x4 w = pack8<T>(v);
                     if (in_range(row))
-                        st_stream(reinterpret_cast<u32x4*>(reinterpret_cast<char*>(g.C) + ((size_t)row * g.ldc + col_base + 32 * p) * 2), w);
+                        *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(g.C) + ((size_t)row * g.ldc + col_base + 32 * p) * 2) = w;
                 }
             }
         }
@@ -400,7 +402,7 @@ __device__ __forceinline__ void epilogue_wave(const GemmArgs& g, f32x4 (&acc)[MI
                     const size_t orow = g.row_map ? (size_t)g.row_map[row] : (size_t)row;
 #pragma unroll
                     for (int p = 0; p < NP; ++p)
-                        st_stream(reinterpret_cast<u32x4*>(reinterpret_cast<char*>(g.C) + (orow * g.ldc + col_base + 32 * p) * 2), packed[i][p]);
+                        *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(g.C) + (orow * g.ldc + col_base + 32 * p) * 2) = packed[i][p];
                 }
             }
         } else {
@@ -413,8 +415,8 @@ __device__ __forceinline__ void epilogue_wave(const GemmArgs& g, f32x4 (&acc)[MI
 #pragma unroll
                     for (int p = 0; p < NP; ++p) {
                         float* o = C + orow * g.ldc + col_base + 32 * p;
-                        st_stream(reinterpret_cast<f32x4*>(o), acc[i][2 * p]);
-                        st_stream(reinterpret_cast<f32x4*>(o + 4), acc[i][2 * p + 1]);
+                        *reinterpret_cast<f32x4*>(o) = acc[i][2 * p];
+                        *reinterpret_cast<f32x4*>(o + 4) = acc[i][2 * p + 1];
                     }
                 }
             }
@@ -726,49 +728,22 @@ gemm_kernel(GemmArgs g) {
 // in flight => >= 12 slots of flight), one barrier or more before its first reader.  The main
 // loop never drains vmcnt to 0 until no further tile exists.
 // ================================================================================================
-// XCD-owned rows (round 4).  The hardware deals the workgroups of a launch to the 8 XCDs round-robin (workgroup b -> XCD b & 7), and each
-// XCD has its own 4 MiB L2.  XCD x owns a contiguous range of row tiles (as even as 8 allows) and runs ALL their column tiles, so an
-// activation panel crosses the fabric into ONE L2 and a weight panel once per XCD; the grid is padded to 8 x (most row tiles an XCD owns)
-// x tiles_n and the surplus workgroups of the XCDs that own one row tile less exit at once.  N_FAST: the column tiles of a row tile are
-// consecutive (one round = 8 row tiles x 4 column tiles for the N = 1024 GEMMs); otherwise the XCD's row tiles are consecutive.
-// Measured (profiles/r04_fabric_traffic.txt, 20-crop half batch): the ping-pong kernel (fc2: 46 row tiles x 4, ONE round, so uneven
-// ownership costs nothing) reads 255 -> 211 MB per launch across the fabric at unchanged time -- ON.  The direct-B kernel (fc1: 91 row
-// tiles x 16, ~3 rounds) reads 199 -> 156 MB but three XCDs then own 12 row tiles against 11: +9 % work on the critical XCDs, tower
-// 14.9 -> 15.2 ms (two streams) / 16.0 -> 17.1 (one) -- OFF, it keeps the tile-balanced GROUP_M walk.
-#ifndef SLIME_OPT_XCD_ROWS_PP
-#define SLIME_OPT_XCD_ROWS_PP 1
-#endif
-#ifndef SLIME_OPT_XCD_ROWS_DB
-#define SLIME_OPT_XCD_ROWS_DB 0
-#endif
-template <bool N_FAST>
+// XCD-owned rows (round 4), the ping-pong kernel's tile walk.  The hardware deals the workgroups of a launch to the 8 XCDs round-robin
+// (workgroup b -> XCD b & 7), and each XCD has its own 4 MiB L2.  XCD x owns a contiguous range of row tiles (as even as 8 allows) and
+// runs ALL their column tiles, consecutively (one round = 8 row tiles x 4 column tiles for the N = 1024 GEMMs), so an activation panel
+// crosses the fabric into ONE L2 and a weight panel once per XCD; the grid is padded to 8 x (most row tiles an XCD owns) x tiles_n and
+// the surplus workgroups of the XCDs that own one row tile less exit at once.
+// Measured (profiles/r04_fabric_traffic.txt, 20-crop half batch): fc2 (46 row tiles x 4, ONE round) reads 255 -> 211 MB per launch
+// across the fabric at unchanged time.  The direct-B kernel keeps the tile-balanced GROUP_M walk: row ownership made the tower 14.9 ->
+// 15.2 ms (round 4), and an evenly balanced deal 14.56 -> 14.80 ms (round 5, profiles/r05_ab_fragment_staging_xcd_rows.txt).
 __device__ __forceinline__ bool xcd_rows_tile(const int tiles_m, const int tiles_n, int& tm, int& tn) {
     const int b = blockIdx.x, xcd = b & 7, j = b >> 3, q = tiles_m >> 3, r = tiles_m & 7;
     const int first = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q, cnt = q + (xcd < r ? 1 : 0);
     if (j >= cnt * tiles_n) return false;
-    if constexpr (N_FAST) { tm = first + j / tiles_n; tn = j % tiles_n; }
-    else { tm = first + j % cnt; tn = j / cnt; }
+    tm = first + j / tiles_n; tn = j % tiles_n;
     return true;
 }
 static inline int xcd_rows_grid(int tiles_m, int tiles_n) { return 8 * ((tiles_m + 7) / 8) * tiles_n; }
-// BALANCED row ownership (round 5; SLIME_OPT_XCD_ROWS_DB == 2).  Whole-row-tile ownership is uneven (91 row tiles = 3 x 12 + 5 x 11) and
-// on multi-round grids the launch ends with the XCDs that own one more (round 4: fabric reads -20 %, time +2 %).  Here every XCD owns
-// q = tiles_m / 8 row tiles [x q, (x + 1) q) with all their column tiles -- walked row tile fastest, so the XCD's q activation panels
-// stay in its L2 while one weight panel after the other streams through -- and the r = tiles_m % 8 left-over row tiles' r x tiles_n
-// tiles are dealt evenly over all XCDs (column tile by column tile): work per XCD differs by at most one tile, an activation panel
-// enters one L2 (a left-over one: a few), a weight panel enters each L2 once.
-__device__ __forceinline__ bool xcd_rows_tile_balanced(const int tiles_m, const int tiles_n, int& tm, int& tn) {
-    const int b = blockIdx.x, xcd = b & 7, j = b >> 3, q = tiles_m >> 3, r = tiles_m & 7;
-    const int own = q * tiles_n;
-    if (j < own) { tm = xcd * q + j % q; tn = j / q; return true; }
-    const int left = r * tiles_n, per = (left + 7) >> 3, e = (j - own) + xcd * per;
-    if (j - own >= per || e >= left) return false;
-    tm = 8 * q + e % r; tn = e / r;
-    return true;
-}
-static inline int xcd_rows_grid_balanced(int tiles_m, int tiles_n) {
-    return 8 * ((tiles_m >> 3) * tiles_n + (((tiles_m & 7) * tiles_n + 7) >> 3));
-}
 
 #define PP_BARRIER()                                   \
     do {                                               \
@@ -791,24 +766,8 @@ __global__ void __launch_bounds__(512) gemm_pp_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tiles_m = (g.M + BM - 1) / BM, tiles_n = g.N / BN;
-#if SLIME_OPT_XCD_ROWS_PP
     int tm, tn;
-    if (!xcd_rows_tile<true>(tiles_m, tiles_n, tm, tn)) return;
-#else
-    const int nblk = tiles_m * tiles_n;
-    int pid;
-    {
-        const int b = blockIdx.x, xcd = b & 7, q = nblk >> 3, r = nblk & 7;
-        pid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
-    const int GROUP_M = g.group_m > 0 ? g.group_m : 4;   // 4 x 8 tiles per XCD round (measured: 4 >= 2,8 > 16 > 46 by ~1-3 %)
-    const int in_group = GROUP_M * tiles_n;
-    const int group_id = pid / in_group;
-    const int first_m = group_id * GROUP_M;
-    const int gsz = min(tiles_m - first_m, GROUP_M);
-    const int tm = first_m + (pid % in_group) % gsz;
-    const int tn = (pid % in_group) / gsz;
-#endif
+    if (!xcd_rows_tile(tiles_m, tiles_n, tm, tn)) return;
     const int m0 = tm * BM, n0 = tn * BN;
 
     unsigned long long t_start = 0, t_pro = 0, t_loop = 0;
@@ -1224,13 +1183,6 @@ __global__ void __launch_bounds__(256, 2) gemm_db_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tiles_m = (g.M + TROWS - 1) / TROWS, tiles_n = g.N / BN;
-#if SLIME_OPT_XCD_ROWS_DB == 2
-    int tm, tn;
-    if (!xcd_rows_tile_balanced(tiles_m, tiles_n, tm, tn)) return;
-#elif SLIME_OPT_XCD_ROWS_DB
-    int tm, tn;
-    if (!xcd_rows_tile<false>(tiles_m, tiles_n, tm, tn)) return;
-#else
     const int nblk = tiles_m * tiles_n;
     int pid;
     {
@@ -1243,7 +1195,6 @@ __global__ void __launch_bounds__(256, 2) gemm_db_kernel(GemmArgs g) {
     const int gsz = min(tiles_m - first_m, GROUP_M);
     const int tm = first_m + (pid % in_group) % gsz;
     const int tn = (pid % in_group) / gsz;
-#endif
     const int m0 = tm * TROWS, n0 = tn * BN;
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1899,12 +1850,7 @@ static int launch_pp_k(const GemmArgs& g, hipStream_t stream) {
     auto kern = gemm_pp_kernel<T, EPI, KTAG, ABL, MT>;
     SLIME_SET_LDS_ONCE(kern, LDS, "gemm_pp");
     const int tiles_m = (g.M + BM - 1) / BM, tiles_n = g.N / 256;
-#if SLIME_OPT_XCD_ROWS_PP
-    const int grid = xcd_rows_grid(tiles_m, tiles_n);
-#else
-    const int grid = tiles_m * tiles_n;
-#endif
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, stream, g);
+    hipLaunchKernelGGL(kern, dim3(xcd_rows_grid(tiles_m, tiles_n)), dim3(512), LDS, stream, g);
     SLIME_CHECK_LAUNCH("gemm_pp");
     return SLIME_OK;
 }
@@ -1964,14 +1910,7 @@ static int launch_db_k(const GemmArgs& g, hipStream_t stream) {
     auto kern = gemm_db_kernel<T, EPI, KTAG, MI>;
     constexpr int TROWS = EPI == SLIME_EPI_BIAS_GELU_MIX_T ? BM / 2 : BM;       // tokens per tile (gemm_db_kernel)
     const int tiles_m = (g.M + TROWS - 1) / TROWS, tiles_n = g.N / 256;
-#if SLIME_OPT_XCD_ROWS_DB == 2
-    const int grid = xcd_rows_grid_balanced(tiles_m, tiles_n);
-#elif SLIME_OPT_XCD_ROWS_DB
-    const int grid = xcd_rows_grid(tiles_m, tiles_n);
-#else
-    const int grid = tiles_m * tiles_n;
-#endif
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDS, stream, g);
+    hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(256), LDS, stream, g);
     SLIME_CHECK_LAUNCH("gemm_db");
     return SLIME_OK;
 }
@@ -1986,12 +1925,13 @@ static int launch_db(const GemmArgs& g, hipStream_t stream) {
 // tiles 16 / 17, in their own translation unit of the diagnostic library.
 bool slime_diag_ps_usable(const GemmArgs& g, int epi);
 int slime_diag_launch_ps(const GemmArgs& g, int dtype, int epi, int tile, hipStream_t stream);
-#endif
 
+// 192 x 256 ping-pong tiles (tile 9): measured alternative for the sub-round grids, see auto_tile
 template <typename T, int EPI>
 static int launch_pp192(const GemmArgs& g, hipStream_t stream) {
     return g.K >= 2048 ? launch_pp_k<T, EPI, 1, 0, 3>(g, stream) : launch_pp_k<T, EPI, 0, 0, 3>(g, stream);
 }
+#endif
 
 template <typename T, int BM, int BN, int WAVES_M, int WAVES_N, int EPI, int SCHED>
 static int launch_cfg(const GemmArgs& g, hipStream_t stream) {
@@ -2008,17 +1948,9 @@ static int launch_cfg(const GemmArgs& g, hipStream_t stream) {
 // Tile choice (a pure function of the shape and of the device's CU count).  The 256-row stream / ping-pong kernels are the
 // throughput kernels; 128x128 (4 waves, 64 KiB LDS, 2 WG/CU) covers narrow N (tiny geometries) and small M.  Partial last
 // rounds of workgroups are filled by running two half batches on two streams (see HipCLIPVisionModel.encode), not by
-// shrinking the tile.  Tile ids: 1 = 256x256 lock-step, 3 = 128x128, 4 = 256x256 ping-pong, 9 = 192x256 ping-pong, 10 / 11 =
-// 192x256 / 256x256 four-wave stream kernel, 12 = 128x256 direct-B kernel (needs Bf), 15 = 128x128 with a three-stage ring; diagnostic build only: 5 = persistent ping-pong, 7 = 2-phase 32x32x16 ping-pong.
-#ifndef SLIME_OPT_TILE64
-#define SLIME_OPT_TILE64 1
-#endif
-#ifndef SLIME_OPT_PP192
-#define SLIME_OPT_PP192 0
-#endif
-#ifndef SLIME_OPT_DB96
-#define SLIME_OPT_DB96 0      // measured alternative (round 6): see auto_tile -- below the 1 % kill rule on the second lease, compiled out
-#endif
+// shrinking the tile.  Tile ids: 1 = 256x256 lock-step, 3 = 128x128, 4 = 256x256 ping-pong, 10 / 11 = 192x256 / 256x256 four-wave
+// stream kernel, 12 = 128x256 direct-B kernel (needs Bf), 15 = 128x128 with a three-stage ring, 18 = 64x64 on that ring; diagnostic
+// build only: 5 = persistent ping-pong, 7 = 2-phase 32x32x16 ping-pong, 9 = 192x256 ping-pong, 13 / 19 = 64x256 / 96x256 direct-B.
 static int auto_tile(const GemmArgs& g) {
     int tile = (g.N % 256 == 0 && g.M >= 512) ? 4 : 3;               // ping-pong 256x256, else 128x128
     if (tile == 4) {
@@ -2026,7 +1958,8 @@ static int auto_tile(const GemmArgs& g) {
         // workgroup time (~ rows + a fixed share).  qkv at 11540 rows: 552 tiles of 256 rows = 3 rounds, 732 tiles
         // of 192 rows = 3 rounds of 3/4-size workgroups (772 -> 866 TF/s).  Sub-round grids (out_proj / fc2: 184
         // tiles) would gain even more stand-alone (994 -> 1216 TF/s) but LOSE 2.5 % inside the two-stream tower,
-        // where the idle CUs of a 0.72-round launch are taken by the other stream's kernels: they keep 256 rows.
+        // where the idle CUs of a 0.72-round launch are taken by the other stream's kernels: they keep 256 rows (round 6, fc2 on
+        // 192-row tiles: bench step +0.34 %, profiles/r06_fc2_192row_tile_ab.txt).
         const long cus = num_cus();
         const long tn = g.N / 256;
         const long n256 = ((g.M + 255) / 256) * tn, n192 = ((g.M + 191) / 192) * tn;
@@ -2043,11 +1976,6 @@ static int auto_tile(const GemmArgs& g) {
         // wins everywhere but on sub-round K = 4096 grids (fc2 at 11540 rows: 184 tiles, 0.96-1.0x), most at small batches
         // (2885 rows: fc1 669 -> 857, qkv 564 -> 649 TF/s); the two-stream tower is 2.5-3 % faster with qkv / out_proj / fc1 on it.
         if (tile != 3 && g.Bf && (n256 >= cus || g.K <= 2048)) tile = 12;
-#if SLIME_OPT_PP192
-        // measured alternative (round 6 re-measurement of the rule's first paragraph with today's kernels): sub-round ping-pong grids
-        // (fc2 at the 20-crop half batch: 184 tiles) on 192-row tiles (244 tiles = 0.95 of a round)
-        if (tile == 4 && n256 < cus && n192 <= cus) tile = 9;
-#endif
     }
     // ... and K > 2048 grids (fc2) in the band where the rule above falls back to the two-stage 128 x 128 kernel although its grid
     // exceeds one workgroup per CU (half batches of 8-12 crops): the direct-B kernel's two-k-step fragment flight covers an under-
@@ -2058,30 +1986,14 @@ static int auto_tile(const GemmArgs& g) {
     // (tower over 1 / 3 / 5 crops 3.12 -> 2.40 / 3.25 -> 2.75 / 3.68 -> 3.18 ms; beyond one workgroup per CU the two-stage form's second
     // resident workgroup is worth more: 9 crops 4.78 vs 5.10 -- tools/rank_shapes.py, profiles/r03_small_batch_latency_c.txt)
     if (tile == 3 && (long)((g.M + 127) / 128) * (g.N / 128) <= num_cus()) tile = 15;
-    // Measured alternative, OFF (round 6, VERDICT r5 item 4: a row-tile height that fills the round): 96 x 256 direct-B tiles (tile 19,
-    // gemm_db_kernel<.., 6>; bit-identical: same k order per accumulator, same epilogue).  Stand-alone the quantisation argument holds
-    // for the sub-round launches -- out_proj at 20 crops 43.7 -> 39.8 us (364 -> 484 workgroups in 512 slots), fc2 at 9 crops 70.0 -> 65.2,
-    // q/k/v at 5 crops 30.5 -> 27.1 -- and fails for the multi-round ones (q/k/v, fc1 at 20 crops: +3 / +6 %: the per-workgroup prologue /
-    // epilogue of the extra tiles costs more than the round returns).  Inside the product's stream policy it buys nothing robust: as a
-    // rule for every direct-B grid that fits one round of slots it is ahead on one stream and 2-5 % BEHIND when two half batches co-run
-    // (10 / 12 / 21 / 24 crops), and out_proj on it costs the bench step 0.3-0.5 %; narrowed to fc2 at 8-10 crops per stream (96-row grid
-    // <= one workgroup per CU) it measured -2.6 / -1.7 / -1.3 % at 16 / 17 / 20 crops on one lease and -0.75 / -1.3 / -0.3 % (+1.7 % at
-    // 21) on the next -- below the 1 % kill rule.  profiles/r06_tile_ab_attention_conflict.txt, r06_small_tiles.txt,
-    // r06_db96_first_rule_ab.txt, r06_db96_narrow_rule_ab.txt.
-#if SLIME_OPT_DB96
-    if (tile == 12 && g.K > 2048 && (long)((g.M + 95) / 96) * (g.N / 256) <= (long)num_cus()) tile = 19;
-#endif
+    // Rejected (round 6): fc2's direct-B grids of at most one 96-row workgroup per CU (K > 2048) on 96 x 256 tiles (tile 19, diagnostic
+    // build only): -2.6 / -1.7 / -1.3 % at 16 / 17 / 20 crops on one lease, -0.75 / -1.3 / -0.3 % (+1.7 % at 21) on the next, below the
+    // 1 % kill rule (profiles/r06_db96_narrow_rule_ab.txt; wider rules: r06_db96_first_rule_ab.txt, r06_tile_ab_attention_conflict.txt).
     // ... and grids that leave HALF the CUs without even a 128 x 128 workgroup (one to three crops: BASELINE config 1, the smallest rank
     // shards) run 64 x 64 tiles on the same three-stage ring (tile 18, round 5): four times the workgroups, and a wave's chain per k-tile
     // is 8 MFMAs instead of 32 -- these launches are bound by that dependent chain (fc2 at one crop: 40 workgroups x 64 k-tiles), not by
     // throughput.  Same k order per accumulator, same epilogue: bit-identical to every other tile.
-#if SLIME_OPT_TILE64 == 2      // measured alternative: every grid of at most one 128 x 128 workgroup per CU (tools/small_latency_ab.py)
-    if (tile == 15) tile = 18;
-#elif SLIME_OPT_TILE64 == 3    // measured alternative: the same, for the long-K launches only (fc2: 64 k-tiles per workgroup): slower from 4 crops on
-    if (tile == 15 && (g.K >= 2048 || (long)((g.M + 127) / 128) * (g.N / 128) * 2 <= num_cus())) tile = 18;
-#elif SLIME_OPT_TILE64
     if (tile == 15 && (long)((g.M + 127) / 128) * (g.N / 128) * 2 <= num_cus()) tile = 18;
-#endif
     return tile;
 }
 
@@ -2098,16 +2010,12 @@ extern "C" void slime_gemm_set_shape_tile(int N, int K, int tile) {
         if (g_rule_n[i] == N && g_rule_k[i] == K) { g_rule_tile[i] = tile; return; }
     if (g_rules < 8) { g_rule_n[g_rules] = N; g_rule_k[g_rules] = K; g_rule_tile[g_rules] = tile; ++g_rules; }
 }
-#endif
-
-// epilogues the 96-row direct-B tile is built for: fc2's (the one launch the dispatch gives it); the diagnostic build adds the tower's
-// other two for the per-shape A/B tools (tools/r6_tile_ab.py, r6_small_tiles.py).  Every other epilogue keeps 128 rows.
+// epilogues the 96-row direct-B tile (tile 19) is built for: the tower's three, for the per-shape A/B tools (tools/r6_tile_ab.py,
+// r6_small_tiles.py).  Every other epilogue keeps 128 rows.
 constexpr bool db96_epilogue(int epi) {
-#ifdef SLIME_DIAG
-    if (epi == SLIME_EPI_BIAS_T || epi == SLIME_EPI_BIAS_QUICKGELU_T) return true;
-#endif
-    return epi == SLIME_EPI_BIAS_RESID_SPLIT_LN;
+    return epi == SLIME_EPI_BIAS_T || epi == SLIME_EPI_BIAS_QUICKGELU_T || epi == SLIME_EPI_BIAS_RESID_SPLIT_LN;
 }
+#endif
 
 template <typename T, int EPI>
 static int launch_epi(const GemmArgs& g, hipStream_t stream) {
@@ -2127,9 +2035,7 @@ static int launch_epi(const GemmArgs& g, hipStream_t stream) {
     if (tile == 5 && g.K < 128) tile = 4;                              // persistent kernel needs >= 2 k-tiles
     if (tile == 5 && ((size_t)g.M * g.lda * 2 >= (1ull << 32) || (size_t)g.N * g.K * 2 >= (1ull << 32))) tile = 4;   // 32-bit row offsets
     if (tile == 5) return launch_ppp<T, EPI>(g, stream);
-#if !SLIME_OPT_PP192
     if (tile == 9) return launch_pp192<T, EPI>(g, stream);
-#endif
     if (tile == 1) return g_sched == 0 ? launch_cfg<T, 256, 256, 2, 4, EPI, 0>(g, stream) : launch_cfg<T, 256, 256, 2, 4, EPI, 1>(g, stream);
     if (tile == 3 && g_sched == 0) return launch_cfg<T, 128, 128, 2, 2, EPI, 0>(g, stream);
 #endif
@@ -2142,22 +2048,17 @@ static int launch_epi(const GemmArgs& g, hipStream_t stream) {
     // B = NULL (the caller holds the fragment-order image only): the lock-step, ping-pong and direct-B kernels read it; the stream
     // kernel (never picked by auto_tile when a fragment image exists) is replaced by the direct-B kernel, or the ping-pong one
     if (!g.B && (tile == 10 || tile == 11)) tile = g.Bf ? 12 : 4;
-#if SLIME_OPT_PP192
-    if (tile == 9) return launch_pp192<T, EPI>(g, stream);
-#endif
     if (tile == 15) return launch_cfg<T, 128, 128, 2, 2, EPI, 2>(g, stream);      // 128 x 128, three-stage ring (small grids)
     if (tile == 18) return launch_cfg<T, 64, 64, 4, 1, EPI, 2>(g, stream);        // 64 x 64, three-stage ring (the smallest grids)
     if (tile == 12) return launch_db<T, EPI, 8>(g, stream);
-    if (tile == 19) {                                             // 96-row direct-B tiles: instantiated for the tower's epilogues (db96_epilogue)
+#ifdef SLIME_DIAG
+    if (tile == 19) {                                             // measured alternative (96-row direct-B tiles), see auto_tile
         if constexpr (db96_epilogue(EPI)) {
             if (g.Bf) return launch_db<T, EPI, 6>(g, stream);
         }
         return launch_db<T, EPI, 8>(g, stream);
     }
-#ifdef SLIME_DIAG
     if (tile == 13) return launch_db<T, EPI, 4>(g, stream);       // measured alternative (64-row direct-B tiles), see gemm_db_kernel
-#else
-    if (tile == 13) return launch_db<T, EPI, 8>(g, stream);
 #endif
     if (tile == 4) return launch_pp<T, EPI>(g, stream);
     if (tile == 10) return launch_w4<T, EPI, 6>(g, stream);
@@ -2191,9 +2092,8 @@ extern "C" int slime_gemm_kernel_name(int M, int N, int K, int dtype, int epilog
     const int tile = auto_tile(g);
     const char* t = dtype == SLIME_F16 ? "F16" : "BF16";
     const int ktag = K >= 2048 ? 1 : 0;
-    if (tile == 19) snprintf(out, out_len, "gemm_db_kernel<%s, %d, %d, %d>", t, epilogue, ktag, db96_epilogue(epilogue) ? 6 : 8);
-    else if (tile == 12 || tile == 13) snprintf(out, out_len, "gemm_db_kernel<%s, %d, %d, %d>", t, epilogue, ktag, tile == 12 ? 8 : 4);
-    else if (tile == 4 || tile == 9) snprintf(out, out_len, "gemm_pp_kernel<%s, %d, %d, 0, %d>", t, epilogue, ktag, tile == 4 ? 4 : 3);
+    if (tile == 12) snprintf(out, out_len, "gemm_db_kernel<%s, %d, %d, 8>", t, epilogue, ktag);
+    else if (tile == 4) snprintf(out, out_len, "gemm_pp_kernel<%s, %d, %d, 0, 4>", t, epilogue, ktag);
     else if (tile == 10 || tile == 11) snprintf(out, out_len, "gemm_w4_kernel<%s, %d, %d, %d, 0>", t, epilogue, ktag, tile == 10 ? 6 : 8);
     else if (tile == 18) snprintf(out, out_len, "gemm_kernel<%s, 64, 64, 4, 1, %d, 2>", t, epilogue);
     else snprintf(out, out_len, "gemm_kernel<%s, 128, 128, 2, 2, %d, %d>", t, epilogue, tile == 15 ? 2 : 1);

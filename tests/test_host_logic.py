@@ -471,7 +471,7 @@ def test_xcd_owned_rows_deal_covers_every_tile_once_and_keeps_a_row_tile_in_one_
 
 @pytest.mark.parametrize("tiles_m,tiles_n", [(91, 16), (91, 12), (91, 4), (181, 16), (46, 4), (5, 4), (8, 3), (1, 1), (23, 16), (108, 16)])
 def test_balanced_xcd_row_deal_covers_every_tile_once_and_is_even(tiles_m, tiles_n):
-    """gemm.hip: xcd_rows_tile_balanced / xcd_rows_grid_balanced (round 5, SLIME_OPT_XCD_ROWS_DB == 2), restated: workgroup b runs on XCD
+    """Round 5's rejected balanced XCD row deal of the direct-B GEMM (FINDINGS.md), restated: workgroup b runs on XCD
     b & 7; every (row tile, column tile) exactly once, surplus workgroups exit; the XCDs' tile counts differ by at most the rounding of
     the left-over share; a whole-owned row tile's column tiles all sit on ONE XCD."""
     q, r = tiles_m >> 3, tiles_m & 7

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""A/B of product-library variants (tools/build_variants.sh) on the 40-crop tower: each variant runs in its own process (one library
-per process), rounds interleaved; prints ms per 40 crops (two streams x 20 | one stream x 40) and a checksum of the features so that
-bit-equality across variants is visible.  usage: lib_variant_ab.py [--rounds R] name[@KEY=VAL[,KEY=VAL]] ...   (name 'product' =
-slime_amd/libslime_hip.so; the optional @ part sets environment variables for that variant's process, e.g. product@SLIME_KEEP_ROW_MAJOR=1)"""
+"""A/B of product libraries on the 40-crop tower (a variant NAME is a product library built from another tree of the same ABI, placed
+as slime_amd/variants/libslime_hip_NAME.so): each variant runs in its own process (one library per process), rounds interleaved; prints
+ms per 40 crops (two streams x 20 | one stream x 40) and a checksum of the features so that bit-equality across variants is visible.
+usage: lib_variant_ab.py [--rounds R] name[@KEY=VAL[,KEY=VAL]] ...   (name 'product' = slime_amd/libslime_hip.so; the optional @ part
+sets environment variables for that variant's process, e.g. product@SLIME_KEEP_ROW_MAJOR=1)"""
 import os, sys, subprocess, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
