@@ -6,8 +6,9 @@ checks, without a GPU, that the product library exports every symbol the header 
 
 Two builds of the same sources exist (slime_amd/csrc/Makefile):
   * ``libslime_hip.so``       the product: the header's entry points, no mutable process state;
-  * ``libslime_hip_diag.so``  ``-DSLIME_DIAG``: adds process-global tuning / ablation hooks and the measured-alternative GEMM
-                              kernels.  Only ``tools/`` and the tile-forcing tests load it (``load_diag()`` / ``diag()``).
+  * ``libslime_hip_diag.so``  ``-DSLIME_DIAG``: adds process-global tuning / ablation hooks and the measured-alternative GEMM and
+                              attention kernels (csrc/gemm_diag.inc, attention_diag.inc, gemm_ps.hip).  Only ``tools/`` and the
+                              tile-forcing tests load it (``load_diag()`` / ``diag()``).
 """
 from __future__ import annotations
 

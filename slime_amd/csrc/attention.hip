@@ -294,7 +294,8 @@ static int launch_attn(const AttnArgs& a0, int batch, hipStream_t stream) {
 
 // ================================================================================================
 // attn64_kernel: the CLIP self-attention shape (head_dim 64, n_kv <= 608 so K and V of one head are
-// LDS resident), software pipelined.
+// LDS resident), software pipelined.  Round 1's kernel, a measured alternative since attn64r_kernel: the kernel and its launcher
+// are in attention_diag.inc, its body and the LDS helpers it shares with attn64r_pass are here.
 //
 // Stamps of the generic kernel above showed 17k of ~95k cycles per workgroup in register-staged K/V
 // loading and ~390 cycles per (16-query sub-block x 32-kv step) against 128 of MFMA: within a wave the
@@ -574,26 +575,6 @@ __device__ __forceinline__ void attn64_body(const AttnArgs& a, char* smem, const
     }
 }
 
-template <typename T>
-__global__ void __launch_bounds__(512) attn64_kernel(AttnArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NW = 8;
-    const int h = blockIdx.x, b = blockIdx.y;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int total_sb = (a.n_q + 15) >> 4;
-    const int wg_sb0 = blockIdx.z * a.sb_per_wg;
-    const int nsb = min(a.sb_per_wg, total_sb - wg_sb0);
-    const int base = nsb / NW, rem = nsb % NW;
-    const int cnt = base + (wave < rem ? 1 : 0);
-    const int sb0 = wg_sb0 + wave * base + min(wave, rem);
-    switch (cnt) {
-        case 0: attn64_body<T, 0>(a, smem, b, h, sb0); break;
-        case 1: attn64_body<T, 1>(a, smem, b, h, sb0); break;
-        case 2: attn64_body<T, 2>(a, smem, b, h, sb0); break;
-        default: attn64_body<T, 3>(a, smem, b, h, sb0); break;
-    }
-}
-
 // ================================================================================================
 // attn64r_kernel: ONE workgroup per (crop, head) -- K and V travel HBM/L2 -> LDS once instead of twice.
 //
@@ -609,7 +590,7 @@ __global__ void __launch_bounds__(512) attn64_kernel(AttnArgs a) {
 // the whole panel at once made every workgroup's first granule queue behind everybody else's panels).
 // ================================================================================================
 // RING (rows, a power of two; 0 = the resident 608-row panel): K and V live in a ring of RING rows each -- granule gi sits in slot
-// gi mod (RING / 8 NW) -- so a workgroup needs 2 x RING x 128 bytes of LDS instead of 152 KiB (attn64g_kernel below).
+// gi mod (RING / 8 NW) -- so a workgroup needs 2 x RING x 128 bytes of LDS instead of 152 KiB (attn64g_kernel, attention_diag.inc).
 // VABL (diagnostic build, variant 40; WRONG results, right timing): the eight ds_read_b64_tr_b16 V^T reads of a kv step are replaced
 // by eight plain ds_read_b64 of the same step's 4 KiB at lane-linear addresses (64 lanes x 8 B = every bank exactly once per pass:
 // conflict free) -- the same number of LDS instructions, bytes and waits without the 2-way bank conflict.  The difference to the
@@ -1009,99 +990,6 @@ __global__ void __launch_bounds__(512) attn64r_kernel(AttnArgs a) {
 #endif
 }
 
-// Twelve-wave variant: three waves per SIMD (<= 2 sub-blocks each, <= 168 VGPRs) instead of two with three sub-blocks.
-// rocprofv3 on attn64r: 36 % of the wave cycles are parked at s_waitcnt / s_barrier and 33 % stalled at issue -- latency, not
-// throughput -- so the third wave per SIMD is there to cover the other two's waits.  24 sub-blocks per workgroup at most,
-// i.e. always two workgroups per CLIP (crop, head); pass 1 only.
-template <typename T>
-__global__ void __launch_bounds__(768) attn64w_kernel(AttnArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NW = 12;
-    const int h = blockIdx.x, b = blockIdx.y;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int total_sb = (a.n_q + 15) >> 4;
-    const int wg_sb0 = blockIdx.z * a.sb_per_wg;
-    const int nsb = min(a.sb_per_wg, total_sb - wg_sb0);      // <= 2 * NW
-    const int base = nsb / NW, rem = nsb % NW;
-    const int cnt = base + (wave < rem ? 1 : 0);
-    const int sb0 = wg_sb0 + wave * base + min(wave, rem);
-    switch (cnt) {
-        case 0: attn64r_pass<T, 0, false, NW, false>(a, smem, b, h, sb0); break;
-        case 1: attn64r_pass<T, 1, false, NW, false>(a, smem, b, h, sb0); break;
-        default: attn64r_pass<T, 2, false, NW, false>(a, smem, b, h, sb0); break;
-    }
-}
-
-template <typename T>
-static int launch_attn64w(const AttnArgs& a0, int batch, hipStream_t stream) {
-    AttnArgs a = a0;
-    constexpr int LDS = 2 * 608 * 128;
-    auto kern = attn64w_kernel<T>;
-    SLIME_SET_LDS_ONCE(kern, LDS, "attention");
-    const int total_sb = (a.n_q + 15) / 16;
-    const int qsplit = (total_sb + 23) / 24;
-    a.sb_per_wg = (total_sb + qsplit - 1) / qsplit;
-    hipLaunchKernelGGL(kern, dim3(a.heads, batch, qsplit), dim3(768), LDS, stream, a);
-    SLIME_CHECK_LAUNCH("attention64w");
-    return SLIME_OK;
-}
-
-#ifdef SLIME_DIAG
-// ================================================================================================
-// attn64g_kernel (round 4, measured alternative): the same pass on a K/V RING -- four waves, 2 x 32 KiB of LDS, <= 256 registers --
-// so that an attention workgroup no longer monopolises its CU (attn64r: 152 KiB + 8 waves x 245 registers) but can share it with
-// another attention workgroup or with a direct-B GEMM workgroup of the tower's other stream (4 waves x 256 registers, 33 KiB):
-// VALU / LDS-heavy softmax waves beside MFMA / L2-bound GEMM waves.  12 query sub-blocks per workgroup (3 per wave), i.e. four
-// workgroups per CLIP (crop, head), each streaming the whole K/V once through the ring (granule = 32 rows = one step, 8 slots,
-// 4 ahead).  One-dimensional grid: the four workgroups of an item are 8 apart in launch order -- same XCD, same L2 -- and items
-// of 8 consecutive heads fill the 8 XCDs.  Same arithmetic in the same order per query sub-block: bit-identical to attn64r.
-// Measured (tools/attn_ring_ab.py, profiles/r04_attention_ring.txt): stand-alone 52 -> 46-48 us at 20 crops, 87 -> 81-83 at 40,
-// 16 -> 13.4 at one crop, equal at 5-9; the two-stream tower 15.28-15.34 -> 15.51-15.52 ms (SLOWER), one stream equal.  Like attn32
-// in rounds 2-3: under the power cap a faster attention that does the same work moves the step nowhere.  Diagnostic build only.
-// ================================================================================================
-template <typename T>
-__global__ void __launch_bounds__(256, 2) attn64g_kernel(AttnArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NW = 4, AHEAD = 4, RING = 256;
-    const int qsplit = a.sb_per_wg >> 16, sb_per_wg = a.sb_per_wg & 0xffff;
-    // launch index -> (item, split): id = 8 qsplit (item / 8) + 8 split + item % 8
-    const int id = blockIdx.x, grp = id / (8 * qsplit), rem = id % (8 * qsplit);
-    const int item = grp * 8 + (rem & 7), split = rem >> 3;
-    if (item >= a.n_items) return;                            // the grid is padded to whole groups of 8 items
-    const int h = item % a.heads, b = item / a.heads;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int total_sb = (a.n_q + 15) >> 4;
-    const int wg_sb0 = split * sb_per_wg;
-    const int nsb = max(0, min(sb_per_wg, total_sb - wg_sb0));     // <= 3 * NW
-    const int base = nsb / NW, rm = nsb % NW;
-    const int cnt = base + (wave < rm ? 1 : 0);
-    const int sb0 = wg_sb0 + wave * base + min(wave, rm);
-    switch (cnt) {
-        case 0: attn64r_pass<T, 0, false, NW, false, AHEAD, RING>(a, smem, b, h, sb0); break;
-        case 1: attn64r_pass<T, 1, false, NW, false, AHEAD, RING>(a, smem, b, h, sb0); break;
-        case 2: attn64r_pass<T, 2, false, NW, false, AHEAD, RING>(a, smem, b, h, sb0); break;
-        default: attn64r_pass<T, 3, false, NW, false, AHEAD, RING>(a, smem, b, h, sb0); break;
-    }
-}
-
-template <typename T>
-static int launch_attn64g(const AttnArgs& a0, int batch, hipStream_t stream) {
-    AttnArgs a = a0;
-    constexpr int LDS = 2 * 256 * 128;
-    auto kern = attn64g_kernel<T>;
-    SLIME_SET_LDS_ONCE(kern, LDS, "attention");
-    const int total_sb = (a.n_q + 15) / 16;
-    const int qsplit = (total_sb + 11) / 12;                  // <= 3 sub-blocks per wave, 4 waves
-    const int per = (total_sb + qsplit - 1) / qsplit;
-    a.sb_per_wg = (qsplit << 16) | per;
-    a.n_items = a.heads * batch;
-    const int groups = (a.n_items + 7) / 8;
-    hipLaunchKernelGGL(kern, dim3(groups * 8 * qsplit), dim3(256), LDS, stream, a);
-    SLIME_CHECK_LAUNCH("attention64g");
-    return SLIME_OK;
-}
-#endif  // SLIME_DIAG
-
 template <typename T, int AHEAD = 3, int VABL = 0>
 static int launch_attn64r(const AttnArgs& a0, int batch, hipStream_t stream) {
     AttnArgs a = a0;
@@ -1124,32 +1012,8 @@ static int launch_attn64r(const AttnArgs& a0, int batch, hipStream_t stream) {
     return SLIME_OK;
 }
 
-template <typename T>
-static int launch_attn64(const AttnArgs& a0, int batch, hipStream_t stream) {
-    AttnArgs a = a0;
-    constexpr int LDS = 2 * 608 * 128;
-    auto kern = attn64_kernel<T>;
-    SLIME_SET_LDS_ONCE(kern, LDS, "attention");
-    const int total_sb = (a.n_q + 15) / 16;
-    const int qsplit = (total_sb + 23) / 24;                  // <= 3 sub-blocks per wave, 8 waves
-    a.sb_per_wg = (total_sb + qsplit - 1) / qsplit;
-    hipLaunchKernelGGL(kern, dim3(a.heads, batch, qsplit), dim3(512), LDS, stream, a);
-    SLIME_CHECK_LAUNCH("attention64");
-    return SLIME_OK;
-}
-
-#include "attention32.inc"
-
-#ifdef SLIME_DIAG   // diagnostic build only (libslime_hip_diag.so): the product library has no mutable globals
-static unsigned long long* g_attn_dbg = nullptr;
-static int g_attn_abl = 0;
-extern "C" void slime_attention_set_ablation(int v) { g_attn_abl = v; }
-static int g_attn_variant = 0;      // 1 = force the generic kernel
-extern "C" void slime_attention_set_variant(int v) { g_attn_variant = v; }
-extern "C" void slime_attention_set_debug(void* p) { g_attn_dbg = (unsigned long long*)p; }
-#else
-static constexpr unsigned long long* g_attn_dbg = nullptr;
-static constexpr int g_attn_abl = 0, g_attn_variant = 0;
+#ifdef SLIME_DIAG   // hooks, measured-alternative kernels and the forced variants: libslime_hip_diag.so only
+#include "attention_diag.inc"
 #endif
 
 extern "C" int slime_attention(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs,
@@ -1164,9 +1028,13 @@ extern "C" int slime_attention(const void* q, long q_bs, long q_rs, const void* 
     SLIME_REQUIRE(batch <= 65535, "attention: batch %d exceeds grid.y", batch);
     SLIME_REQUIRE(dtype == SLIME_BF16 || dtype == SLIME_F16, "attention: dtype %d is not a 16-bit MFMA type", dtype);
     AttnArgs a{(const char*)q, q_bs, q_rs, (const char*)k, k_bs, k_rs, (const char*)v, v_bs, v_rs,
-               (char*)o, o_bs, o_rs, heads, n_q, n_kv, 0, g_attn_dbg, g_attn_abl};
+               (char*)o, o_bs, o_rs, heads, n_q, n_kv, 0, /*dbg*/ nullptr, /*abl*/ 0};
     hipStream_t s = (hipStream_t)stream;
-    if (head_dim == 64 && n_kv <= 608 && n_kv >= 321 && g_attn_variant == 0 && !g_attn_dbg) {
+    bool clip_shape = head_dim == 64 && n_kv <= 608 && n_kv >= 321;
+#ifdef SLIME_DIAG
+    if (const auto rc = diag_attention(a, clip_shape, batch, head_dim, n_kv, dtype, s)) return *rc;    // hooks and forced variants
+#endif
+    if (clip_shape) {
         // CLIP shape: software-pipelined kernel, one or two workgroups per (crop, head), K/V staged once (granule DMA).
         // Round 3 re-measured the one-wave-per-SIMD alternative (attention32.inc, diagnostic variants 4-6) now that the GEMMs run two
         // workgroups per CU: its uncut form is worth 1 % of the 40-crop tower (15.18 -> 15.01 ms, profiles/r03_tower_knobs.txt) but
@@ -1177,45 +1045,6 @@ extern "C" int slime_attention(const void* q, long q_bs, long q_rs, const void* 
         if (dtype == SLIME_F16) return launch_attn64r<F16>(a, batch, s);
         return launch_attn64r<BF16>(a, batch, s);
     }
-#ifdef SLIME_DIAG
-    if (head_dim == 64 && n_kv <= 608 && n_kv >= 321 && g_attn_variant >= 4 && g_attn_variant <= 6 && dtype == SLIME_BF16)
-        return launch_attn32<BF16>(a, batch, g_attn_variant == 5 ? 2 : g_attn_variant == 6 ? -1 : 0, s);
-    if (head_dim == 64 && n_kv <= 608 && n_kv >= 321 && g_attn_variant >= 12 && g_attn_variant <= 15 && dtype == SLIME_BF16)
-        return launch_attn32<BF16>(a, batch, g_attn_variant - 10, s);                       // every item cut in 2 / 3 / 4 / 5
-    if (head_dim == 64 && n_kv <= 608 && n_kv >= 321 && g_attn_variant >= 22 && g_attn_variant <= 27 && dtype == SLIME_BF16) {
-        // attn64r with 2 / 3 / 4 / 6 K/V granules requested ahead, 27: the whole panel up front (rounds 1-2); with or without stamp records
-        switch (g_attn_variant) {
-            case 22: return launch_attn64r<BF16, 2>(a, batch, s);
-            case 23: return launch_attn64r<BF16, 3>(a, batch, s);
-            case 24: return launch_attn64r<BF16, 4>(a, batch, s);
-            case 26: return launch_attn64r<BF16, 6>(a, batch, s);
-            default: return launch_attn64r<BF16, 16>(a, batch, s);
-        }
-    }
-    if (head_dim == 64 && n_kv <= 608 && n_kv >= 321 && g_attn_variant == 40 && dtype == SLIME_BF16 && !g_attn_dbg)
-        return launch_attn64r<BF16, 3, 1>(a, batch, s);      // round 6 timing ablation: conflict-free plain reads instead of the V^T transpose reads (wrong results)
-    if (head_dim == 64 && n_kv <= 608 && n_kv >= 321 && g_attn_variant == 17 && g_attn_dbg) {   // attn64r with one stamp record per workgroup
-        if (dtype == SLIME_F16) return launch_attn64r<F16>(a, batch, s);
-        return launch_attn64r<BF16>(a, batch, s);
-    }
-    if (head_dim == 64 && n_kv <= 608 && n_kv >= 321 && g_attn_variant == 7 && !g_attn_dbg) {    // round 2's product kernel, for A/B
-        if (dtype == SLIME_F16) return launch_attn64r<F16>(a, batch, s);
-        return launch_attn64r<BF16>(a, batch, s);
-    }
-    if (head_dim == 64 && n_kv <= 608 && n_kv >= 321 && g_attn_variant == 30 && !g_attn_dbg) {   // round 4: K/V ring, four waves, two per CU
-        if (dtype == SLIME_F16) return launch_attn64g<F16>(a, batch, s);
-        return launch_attn64g<BF16>(a, batch, s);
-    }
-    if (head_dim == 64 && n_kv <= 608 && n_kv >= 321 && g_attn_variant == 3 && !g_attn_dbg) {
-        if (dtype == SLIME_F16) return launch_attn64w<F16>(a, batch, s);
-        return launch_attn64w<BF16>(a, batch, s);
-    }
-    if (head_dim == 64 && n_kv <= 608 && n_kv >= 321 && g_attn_variant == 2 && !g_attn_dbg) {
-        // the round-1 kernel (two workgroups per (crop, head), two DMA halves), kept for A/B
-        if (dtype == SLIME_F16) return launch_attn64<F16>(a, batch, s);
-        return launch_attn64<BF16>(a, batch, s);
-    }
-#endif
     if (head_dim == 64) {
         // K+V resident up to 608 rows (CLIP S = 577); longer sequences stream in 608-row chunks.
         if (dtype == SLIME_F16) return launch_attn<F16, 64, 608, 8, 5>(a, batch, s);

@@ -1,5 +1,5 @@
 // attention32.inc -- CLIP self-attention (head_dim 64, 321..608 keys) as ONE wave per SIMD on 32x32x16 MFMAs.
-// Included by attention.hip (shares AttnArgs and the inline-asm LDS helpers).
+// Included by attention_diag.inc, i.e. by attention.hip in the diagnostic build only (shares AttnArgs and the inline-asm LDS helpers).
 //
 // attn64r (above) runs two 3-sub-block waves per SIMD and leaves the overlap of the matrix pipe with the softmax VALU
 // stream to the hardware's wave arbitration; rocprofv3 shows it MFMA-busy 17 % of the time with the waves parked or
