@@ -405,6 +405,28 @@ int slime_adapter_forward(const slime_mlp_desc* mlp, const slime_resampler_desc*
                           int n_images, int n_local, int nw, int nh, int merge, void* out, int out_dtype,
                           long out_image_stride, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the same for a batch whose images have DIFFERENT crop layouts (the usual anyres batch: the slicer gives each image 1 to 7
+ * local crops on a grid of its own).  Image i has n_i = nw[i] * nh[i] local crops; the pair 0, 0 is an image without local crops
+ * (post may be NULL when no image has any).  With merge == 0 (flat order) the convention is nw[i] = n_i, nh[i] = 1, as above.
+ *   feats: T [sum_i (1 + n_i), 576, D] in image order, crop 0 of each image = its global view.
+ *   out:   out_dtype [out_rows, H], flat.  Image i owns rows [out_row0[i], out_row0[i] + 576 + n_i*g*g): its gated global tokens,
+ *          then its local tokens in raster order of its own nw[i] x nh[i] grid (merge != 0) or in crop order.  out_row0 == NULL:
+ *          the images are packed back to back.  Rows no image owns are left untouched.
+ *   out_dtype: fp32 or the operand type T (both stored by projection[2] through the row map); another 16-bit type is SLIME_EINVAL.
+ * nw, nh and out_row0 are HOST arrays, read during the call only: the layout reaches the device by value in the arguments of one
+ * small plan kernel (hence at most SLIME_ADAPTER_RAGGED_MAX_IMAGES images), which writes the row map and the crop tables into the
+ * workspace -- no upload, no allocation, capturable.  SLIME_EINVAL, with the limit named: more images than the cap, a grid with
+ * exactly one factor 0, out_row0 ranges that overlap or leave [0, out_rows), out_rows >= 2^31, and the descriptor mismatches
+ * slime_adapter_forward rejects.  Per image the tokens are those of slime_adapter_forward on that image alone (the rows are
+ * independent; only the GEMMs' M differs). */
+#define SLIME_ADAPTER_RAGGED_MAX_IMAGES 64
+size_t slime_adapter_ragged_workspace_bytes(const slime_mlp_desc* mlp, const slime_resampler_desc* attn,
+                                            const slime_resampler_desc* post, int n_images, const int* nw, const int* nh);
+int slime_adapter_forward_ragged(const slime_mlp_desc* mlp, const slime_resampler_desc* attn, const float* w_gate,
+                                 int learnable_gated, const slime_resampler_desc* post, const void* feats, int n_images,
+                                 const int* nw, const int* nh, int merge, void* out, int out_dtype,
+                                 const long long* out_row0, long out_rows, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * After the visual tokens: splice into the text embeddings, Llama prefill attention
  * ---------------------------------------------------------------------------------------------- */

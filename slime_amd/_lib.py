@@ -137,6 +137,10 @@ _SIGNATURES = {
     "slime_adapter_workspace_bytes": (c_size_t, [_P(MlpDesc), _P(ResamplerDesc), _P(ResamplerDesc), c_int, c_int]),
     "slime_adapter_forward": (c_int, [_P(MlpDesc), _P(ResamplerDesc), c_void_p, c_int, _P(ResamplerDesc), c_void_p, c_int, c_int,
                                       c_int, c_int, c_int, c_void_p, c_int, c_long, c_void_p, c_size_t, c_void_p]),
+    "slime_adapter_ragged_workspace_bytes": (c_size_t, [_P(MlpDesc), _P(ResamplerDesc), _P(ResamplerDesc), c_int, _P(c_int), _P(c_int)]),
+    "slime_adapter_forward_ragged": (c_int, [_P(MlpDesc), _P(ResamplerDesc), c_void_p, c_int, _P(ResamplerDesc), c_void_p, c_int,
+                                             _P(c_int), _P(c_int), c_int, c_void_p, c_int, _P(C.c_longlong), c_long, c_void_p, c_size_t,
+                                             c_void_p]),
     "slime_splice_rows": (c_int, [c_void_p, c_int, c_long, c_void_p, c_int, c_long, c_void_p, c_void_p, c_int, c_long, c_int, c_void_p]),
     "slime_rope": (c_int, [c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_float, c_int, c_void_p]),
     "slime_prefill_attention": (c_int, [c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_void_p, c_long,

@@ -5,6 +5,7 @@
 #include <stdarg.h>
 #include <string.h>
 #include "common.h"
+#include "adapter_ragged.h"
 
 static thread_local char g_err[512] = "";
 
@@ -277,7 +278,8 @@ int layernorm_crops_launch(const void* feats, int dtype, int P, int period, int 
 
 // crops != nullptr (fused adapter, round 5): the input rows are the selected crops of the tower's T features, read by the first
 // LayerNorm directly (no fp32 copy of them); otherwise x fp32 [n, n_kv, dim]
-struct ResCrops { const void* feats; int period, first, per_image, images; };
+// (table != nullptr, ragged fused adapter: crop j of the n input crops is feats crop table[j], a DEVICE int32 array)
+struct ResCrops { const void* feats; int period, first, per_image, images; const int* table = nullptr; };
 static int resampler_run(const slime_resampler_desc* d, const float* x, int ldx, const ResCrops* crops, int n, float* out_f32,
                          void* out_t, void* ws, size_t ws_bytes, void* stream) {
     TRY(resampler_validate(d));
@@ -291,7 +293,10 @@ static int resampler_run(const slime_resampler_desc* d, const float* x, int ldx,
     char* w = (char*)ws;
     const int D = d->dim, Rk = n * d->n_kv, Rq = n * d->n_query, dh = D / d->heads, dt = d->dtype;
     // x = ln_kv(x); K input = x + pos (sampler.py:158,164); V input = x
-    if (crops)
+    if (crops && crops->table)
+        TRY(layernorm_crops_indexed_launch(crops->feats, dt, d->n_kv, crops->table, n, D, d->ln_kv_w, d->ln_kv_b, d->eps, w + p.xn, w + p.xk,
+                                           d->pos_k, d->n_kv, stream));
+    else if (crops)
         TRY(layernorm_crops_launch(crops->feats, dt, d->n_kv, crops->period, crops->first, crops->per_image, crops->images, D, d->ln_kv_w,
                                    d->ln_kv_b, d->eps, w + p.xn, w + p.xk, d->pos_k, d->n_kv, stream));
     else
@@ -436,12 +441,13 @@ extern "C" int slime_gated_forward(const slime_mlp_desc* mlp, const slime_resamp
 int adapter_row_map_launch(int* map, long rows_g, int P, long rows_l, long per_image_local, int g, int nw, int merge, long out_image_stride,
                            void* stream);                                   // rowwise.hip (internal)
 struct AdapterPlan { size_t xg32, xl32, stack, e, mlp, res, gates, rmap, total; long rows_g, rows_l, rows_all; int segs_g; };
-static AdapterPlan adapter_plan(const slime_mlp_desc* m, const slime_resampler_desc* attn, const slime_resampler_desc* post,
-                                int n_images, int n_local, int learnable_gated) {
+// total_local = local crops of the whole batch (n_images * n_local for a uniform batch, sum n_i for a ragged one)
+static AdapterPlan adapter_plan_total(const slime_mlp_desc* m, const slime_resampler_desc* attn, const slime_resampler_desc* post,
+                                      int n_images, long total_local, int learnable_gated) {
     AdapterPlan p{};
     const size_t D = m->in_dim, H = m->hidden;
     p.rows_g = (long)n_images * attn->n_kv;
-    p.rows_l = post ? (long)n_images * n_local * post->n_query : 0;
+    p.rows_l = post ? total_local * post->n_query : 0;
     p.segs_g = learnable_gated < 0 ? 2 : 1;
     p.rows_all = p.segs_g * p.rows_g + p.rows_l;
     size_t off = 0;
@@ -452,12 +458,16 @@ static AdapterPlan adapter_plan(const slime_mlp_desc* m, const slime_resampler_d
     p.e = take((size_t)p.rows_all * H * 4);
     p.mlp = take(mlp_plan(m, (int)p.rows_all).total);
     size_t res = res_plan(attn, n_images).total;
-    if (post && n_local > 0) { const size_t r2 = res_plan(post, n_images * n_local).total; if (r2 > res) res = r2; }
+    if (post && total_local > 0) { const size_t r2 = res_plan(post, (int)total_local).total; if (r2 > res) res = r2; }
     p.res = take(res);
     p.gates = take((size_t)p.rows_g * 2 * sizeof(float));
     p.rmap = take((size_t)(p.rows_g + p.rows_l) * sizeof(int));
     p.total = align_up(off, 256);
     return p;
+}
+static AdapterPlan adapter_plan(const slime_mlp_desc* m, const slime_resampler_desc* attn, const slime_resampler_desc* post,
+                                int n_images, int n_local, int learnable_gated) {
+    return adapter_plan_total(m, attn, post, n_images, (long)n_images * n_local, learnable_gated);
 }
 
 extern "C" size_t slime_adapter_workspace_bytes(const slime_mlp_desc* mlp, const slime_resampler_desc* attn,
@@ -571,6 +581,168 @@ extern "C" int slime_adapter_forward(const slime_mlp_desc* mlp, const slime_resa
         if (post)
             TRY(slime_merge_rows_batched(e + (size_t)e_local * H, (long)n_local * post->n_query, out, out_dtype, out_image_stride, P,
                                          n_images, nw, nh, g, H, merge, stream));
+    }
+    return SLIME_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Fused adapter for a batch whose images have DIFFERENT crop layouts: the sequence of slime_adapter_forward with the three places
+// that assumed one layout -- the crops' positions in feats, the rows each image owns in the token buffer, its crop grid -- read
+// from device tables that ONE plan kernel derives from the per-image layout in its kernel arguments.  Every other launch is the
+// uniform call's (resampler_run, gemm_mix / gemm_w, slime_gate_weights / slime_gate_premix, slime_gemm_ex with row_map); the rows
+// are independent, so an image's tokens are those of the uniform call on that image alone up to the GEMM's tile choice.
+// ------------------------------------------------------------------------------------------------
+struct RaggedPlan { AdapterPlan a; size_t gtab, ltab, total; long total_local; };
+
+// host-only: validates the grids and fills the layout (out_row0 == nullptr: packed); *post is cleared when no image has local crops
+static int ragged_layout(const slime_resampler_desc* attn, const slime_resampler_desc** post, int n_images, const int* nw, const int* nh,
+                         int merge, const long long* out_row0, long out_rows, RaggedLayout* L) {
+    SLIME_REQUIRE(n_images > 0 && nw && nh, "adapter_ragged: bad input");
+    SLIME_REQUIRE(n_images <= SLIME_ADAPTER_RAGGED_MAX_IMAGES, "adapter_ragged: %d images, more than SLIME_ADAPTER_RAGGED_MAX_IMAGES = %d (the layout "
+                  "travels in the kernel arguments)", n_images, SLIME_ADAPTER_RAGGED_MAX_IMAGES);
+    long total_local = 0;
+    for (int i = 0; i < n_images; ++i) {
+        SLIME_REQUIRE(nw[i] >= 0 && nh[i] >= 0 && (nw[i] == 0) == (nh[i] == 0), "adapter_ragged: image %d: grid %dx%d (a grid is 0x0 -- no local "
+                      "crops -- or has both factors > 0)", i, nw[i], nh[i]);
+        SLIME_REQUIRE((long)nw[i] * nh[i] <= (1 << 16), "adapter_ragged: image %d: grid %dx%d holds more than 65536 crops", i, nw[i], nh[i]);
+        total_local += (long)nw[i] * nh[i];
+    }
+    int g = 1, q = 1;
+    if (total_local > 0) {
+        SLIME_REQUIRE(*post, "adapter_ragged: local crops without post_qformer");
+        TRY(resampler_validate(*post));
+        q = (*post)->n_query;
+        g = 0;
+        while (g * g < q) ++g;
+        SLIME_REQUIRE(g * g == q, "adapter: post_qformer query count %d is not a square grid", q);
+    } else {
+        *post = nullptr;
+    }
+    const int P = attn->n_kv;
+    SLIME_REQUIRE(out_rows > 0 && out_rows < (1L << 31), "adapter_ragged: token buffer of %ld rows is beyond the 32-bit row map (limit 2^31 - 1 rows)", out_rows);
+    SLIME_REQUIRE(((long)n_images * P + total_local * q) < (1L << 31), "adapter_ragged: %ld token rows are beyond the 32-bit row map", (long)n_images * P + total_local * q);
+    *L = RaggedLayout{};
+    L->n_images = n_images; L->P = P; L->q = q; L->g = g; L->merge = merge ? 1 : 0;
+    long crop = 0, lrow = 0, packed = 0;
+    for (int i = 0; i < n_images; ++i) {
+        const long n = (long)nw[i] * nh[i], rows = P + n * q;
+        const long long r0 = out_row0 ? out_row0[i] : (long long)packed;
+        SLIME_REQUIRE(rows <= out_rows && r0 >= 0 && r0 <= out_rows - rows, "adapter_ragged: image %d: %ld rows from row %lld are outside the token "
+                      "buffer (out_rows = %ld%s)", i, rows, r0, out_rows, out_row0 ? "" : ": too small for the packed images");
+        L->crop0[i] = (int)crop; L->n[i] = (int)n; L->nw[i] = nw[i] > 0 ? nw[i] : 1; L->dst0[i] = (int)r0; L->lrow0[i] = (int)lrow;
+        crop += 1 + n; lrow += n * q; packed += rows;
+    }
+    L->lrow0[n_images] = (int)lrow;
+    if (out_row0)                                                // explicit rows: no two images may share a row (64 images: the plain pair test)
+        for (int i = 0; i < n_images; ++i)
+            for (int j = 0; j < i; ++j) {
+                const long ri = L->dst0[i], ei = ri + P + (long)L->n[i] * q, rj = L->dst0[j], ej = rj + P + (long)L->n[j] * q;
+                SLIME_REQUIRE(ei <= rj || ej <= ri, "adapter_ragged: out_row0 of images %d and %d overlap (rows [%ld, %ld) and [%ld, %ld))", j, i, rj, ej, ri, ei);
+            }
+    return SLIME_OK;
+}
+
+static RaggedPlan ragged_plan(const slime_mlp_desc* m, const slime_resampler_desc* attn, const slime_resampler_desc* post, int n_images,
+                              long total_local, int learnable_gated) {
+    RaggedPlan p{};
+    p.total_local = total_local;
+    p.a = adapter_plan_total(m, attn, post, n_images, total_local, learnable_gated);
+    p.gtab = p.a.total;                                          // 256-B aligned
+    p.ltab = p.gtab + align_up((size_t)n_images * sizeof(int), 256);
+    p.total = p.ltab + align_up((size_t)total_local * sizeof(int), 256);
+    return p;
+}
+
+extern "C" size_t slime_adapter_ragged_workspace_bytes(const slime_mlp_desc* mlp, const slime_resampler_desc* attn,
+                                                       const slime_resampler_desc* post, int n_images, const int* nw, const int* nh) {
+    if (!mlp || !attn || !nw || !nh || n_images <= 0 || n_images > SLIME_ADAPTER_RAGGED_MAX_IMAGES) return 0;
+    long total_local = 0;
+    for (int i = 0; i < n_images; ++i) {
+        if (nw[i] < 0 || nh[i] < 0 || (nw[i] == 0) != (nh[i] == 0) || (long)nw[i] * nh[i] > (1 << 16)) return 0;
+        total_local += (long)nw[i] * nh[i];
+    }
+    if (total_local > 0 && !post) return 0;
+    return ragged_plan(mlp, attn, total_local > 0 ? post : nullptr, n_images, total_local, -1).total;
+}
+
+extern "C" int slime_adapter_forward_ragged(const slime_mlp_desc* mlp, const slime_resampler_desc* attn, const float* w_gate,
+                                            int learnable_gated, const slime_resampler_desc* post, const void* feats, int n_images,
+                                            const int* nw, const int* nh, int merge, void* out, int out_dtype,
+                                            const long long* out_row0, long out_rows, void* ws, size_t ws_bytes, void* stream) {
+    TRY(mlp_validate(mlp));
+    TRY(resampler_validate(attn));
+    SLIME_REQUIRE(feats && out, "adapter_ragged: bad input");
+    SLIME_REQUIRE(attn->dim == mlp->in_dim && attn->n_query == attn->n_kv, "adapter: attn must map the token grid onto itself");
+    SLIME_REQUIRE(learnable_gated >= 0 || w_gate, "adapter: missing w_gate");
+    SLIME_REQUIRE(learnable_gated <= 1, "adapter: expert index %d", learnable_gated);
+    SLIME_REQUIRE(attn->dtype == mlp->dtype, "adapter: mixed operand dtypes");
+    const int P = attn->n_kv, D = mlp->in_dim, H = mlp->hidden, dt = mlp->dtype;
+    SLIME_REQUIRE(out_dtype == SLIME_F32 || out_dtype == dt, "adapter_ragged: out_dtype %d is neither fp32 nor the operand type %d (a 16-bit "
+                  "output type other than the operand type is not stored through the row map: use the per-module path)", out_dtype, dt);
+    RaggedLayout L;
+    TRY(ragged_layout(attn, &post, n_images, nw, nh, merge, out_row0, out_rows, &L));
+    if (post)
+        SLIME_REQUIRE(post->dim == mlp->in_dim && post->n_kv == attn->n_kv && post->dtype == mlp->dtype, "adapter: post_qformer does not match the tower grid");
+    const long total_local = L.lrow0[n_images] / L.q;
+    const RaggedPlan rp = ragged_plan(mlp, attn, post, n_images, total_local, learnable_gated);
+    const AdapterPlan& p = rp.a;
+    if (!ws || ws_bytes < rp.total || ((uintptr_t)ws % 256) != 0) {
+        slime_set_error("adapter_ragged: workspace %zu B (need %zu, 256-B aligned)", ws_bytes, rp.total);
+        return SLIME_EWORKSPACE;
+    }
+    char* w = (char*)ws;
+    float* xg32 = (float*)(w + p.xg32);
+    char* stack = w + p.stack;
+    int* rmap = (int*)(w + p.rmap);
+    int* gtab = (int*)(w + rp.gtab);
+    int* ltab = (int*)(w + rp.ltab);
+
+    // stacked MLP input: [x_global | attn(x_global) | post_qformer(x_local)] (segments that are not needed are dropped)
+    size_t row = 0;
+    long seg_x = -1, seg_attn = -1, seg_local = -1;
+    if (learnable_gated != 1) { seg_x = (long)row; row += p.rows_g; }
+    if (learnable_gated != 0) { seg_attn = (long)row; row += p.rows_g; }
+    if (post) { seg_local = (long)row; row += p.rows_l; }
+
+    // the device tables: projection[2]'s row map and the source crops of the global / local segments
+    TRY(adapter_ragged_plan_launch(L, rmap, gtab, ltab, stream));
+    // global crops: fp32 copy for the resampler's LayerNorm and the gate logits, T copy straight into the stack
+    TRY(select_crops_indexed_launch(feats, dt, P, D, gtab, n_images, xg32, seg_x >= 0 ? stack + (size_t)seg_x * D * 2 : nullptr, stream));
+    if (seg_attn >= 0)
+        TRY(slime_resampler_forward(attn, xg32, D, n_images, nullptr, stack + (size_t)seg_attn * D * 2, w + p.res,
+                                    res_plan(attn, n_images).total, stream));
+    if (post) {
+        // local crops: post_qformer's first LayerNorm reads them straight from the tower's T features, through the crop table
+        const ResCrops rc{feats, 0, 0, 0, 0, ltab};
+        TRY(resampler_run(post, nullptr, 0, &rc, (int)total_local, nullptr, stack + (size_t)seg_local * D * 2, w + p.res,
+                          res_plan(post, (int)total_local).total, stream));
+    }
+    // projection MLP over the stack, as in slime_adapter_forward; projection[2] stores every row through the row map
+    const MlpPlan mp = mlp_plan(mlp, (int)p.rows_all);
+    char* mid = w + p.mlp + mp.mid;
+    auto projection2 = [&](const void* A, int rows) -> int {     // rows = [global | local] rows of the hidden activations
+        slime_gemm_args a{};
+        a.A = A; a.lda = H; a.B = mlp->w2; a.B_frag = mlp->w2_frag; a.bias = mlp->b2; a.M = rows; a.N = H; a.K = H; a.dtype = dt;
+        a.C = out; a.ldc = H; a.row_map = rmap; a.epilogue = out_dtype == SLIME_F32 ? SLIME_EPI_BIAS_F32 : SLIME_EPI_BIAS_T;
+        return slime_gemm_ex(&a, stream);
+    };
+    if (learnable_gated < 0) {
+        char* mixed = mid + (size_t)seg_attn * H * 2;
+        if (mix_in_gemm(mlp)) {
+            float* gates = (float*)(w + p.gates);
+            TRY(slime_gate_weights(xg32, D, w_gate, gates, (int)p.rows_g, stream));
+            TRY(gemm_mix(stack + (size_t)seg_x * D * 2, stack + (size_t)seg_attn * D * 2, gates, mlp, mixed, (int)p.rows_g, stream));
+            if (post)
+                TRY(gemm_w(stack + (size_t)seg_local * D * 2, D, mlp->w1, mlp->w1_frag, mlp->b1, mid + (size_t)seg_local * H * 2, H,
+                           (int)p.rows_l, H, D, dt, SLIME_EPI_BIAS_GELU_T, stream));
+        } else {
+            TRY(gemm_w(stack, D, mlp->w1, mlp->w1_frag, mlp->b1, mid, H, (int)p.rows_all, H, D, dt, SLIME_EPI_BIAS_GELU_T, stream));
+            TRY(slime_gate_premix(xg32, D, w_gate, mid + (size_t)seg_x * H * 2, mixed, mixed, dt, (int)p.rows_g, H, stream));
+        }
+        TRY(projection2(mixed, (int)(p.rows_g + p.rows_l)));
+    } else {
+        TRY(gemm_w(stack, D, mlp->w1, mlp->w1_frag, mlp->b1, mid, H, (int)p.rows_all, H, D, dt, SLIME_EPI_BIAS_GELU_T, stream));
+        TRY(projection2(mid, (int)p.rows_all));
     }
     return SLIME_OK;
 }

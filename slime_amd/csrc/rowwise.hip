@@ -3,6 +3,7 @@
 // since round 5: patch_embed.hip.)
 // One wave (64 lanes) owns one row; loads are 16 B/lane (float4) wherever the width allows.
 #include "common.h"
+#include "adapter_ragged.h"
 
 template <typename T> __device__ __forceinline__ unsigned short to_t1(float x) {
     return (unsigned short)(T::pack2(x, 0.f) & 0xffffu);
@@ -141,6 +142,99 @@ int layernorm_crops_launch(const void* feats, int dtype, int P, int period, int 
     LnArgs a{nullptr, 0, images * per_image * P, w, b, eps, 1, nullptr, out_t, out_t2, add, add_period, (const char*)feats, P, period, first, per_image};
     if (dtype == SLIME_F16) return launch_ln<F16>(a, D, (hipStream_t)stream);
     return launch_ln<BF16>(a, D, (hipStream_t)stream);
+}
+
+// The T-input LayerNorm above with the source crop of selected crop j read from a DEVICE table (ragged fused adapter: row r = crop
+// table[r / P], token r % P) -- a kernel of its own, so that the code of layernorm_kernel, whose last bit is pinned, cannot move.  The
+// arithmetic is layernorm_kernel's, operation for operation (normalize = 1, outputs out_t and optionally out_t2 = T(y + add)).
+struct LnIndexedArgs {
+    const char* xt; const int* table; int P; int rows;
+    const float* w; const float* b; float eps;
+    void* out_t; void* out_t2; const float* add; int add_period;
+};
+
+template <typename T, int VPL>
+__global__ void __launch_bounds__(256) layernorm_indexed_kernel(LnIndexedArgs a) {
+    constexpr int D = 64 * VPL;
+    constexpr int VEC = (VPL >= 4) ? 4 : 2;          // elements per load
+    constexpr int NV = VPL / VEC;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= a.rows) return;
+    float v[VPL];
+    const long crop = a.table[row / a.P], tok = row % a.P;
+    const char* xr = a.xt + ((size_t)crop * a.P + tok) * D * 2;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = (i * 64 + lane) * VEC;
+        if constexpr (VEC == 4) {
+            const u32x2 t = *reinterpret_cast<const u32x2*>(xr + (size_t)c * 2);
+            v[i * 4 + 0] = T::lo(t[0]); v[i * 4 + 1] = T::hi(t[0]); v[i * 4 + 2] = T::lo(t[1]); v[i * 4 + 3] = T::hi(t[1]);
+        } else {
+            const unsigned t = *reinterpret_cast<const unsigned*>(xr + (size_t)c * 2);
+            v[i * 2 + 0] = T::lo(t); v[i * 2 + 1] = T::hi(t);
+        }
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) s += v[i];
+    const float mean = wave_sum(s) * (1.0f / D);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) { const float d = __fsub_rn(v[i], mean); q = __fmaf_rn(d, d, q); }
+    const float rstd = rsqrtf(__fmaf_rn(wave_sum(q), 1.0f / D, a.eps));
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = (i * 64 + lane) * VEC;
+#pragma unroll
+        for (int j = 0; j < VEC; ++j)
+            v[i * VEC + j] = __fmaf_rn(__fmul_rn(__fsub_rn(v[i * VEC + j], mean), rstd), a.w[c + j], a.b[c + j]);
+    }
+    const float* addr = a.out_t2 ? a.add + (size_t)(row % a.add_period) * D : nullptr;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = (i * 64 + lane) * VEC;
+        char* o = reinterpret_cast<char*>(a.out_t) + ((size_t)row * D + c) * 2;
+        if constexpr (VEC == 4) {
+            u32x2 p = {T::pack2(v[i * 4], v[i * 4 + 1]), T::pack2(v[i * 4 + 2], v[i * 4 + 3])};
+            *reinterpret_cast<u32x2*>(o) = p;
+        } else {
+            *reinterpret_cast<unsigned*>(o) = T::pack2(v[i * 2], v[i * 2 + 1]);
+        }
+        if (a.out_t2) {
+            char* o2 = reinterpret_cast<char*>(a.out_t2) + ((size_t)row * D + c) * 2;
+            if constexpr (VEC == 4) {
+                u32x2 p = {T::pack2(v[i * 4] + addr[c], v[i * 4 + 1] + addr[c + 1]),
+                           T::pack2(v[i * 4 + 2] + addr[c + 2], v[i * 4 + 3] + addr[c + 3])};
+                *reinterpret_cast<u32x2*>(o2) = p;
+            } else {
+                *reinterpret_cast<unsigned*>(o2) = T::pack2(v[i * 2] + addr[c], v[i * 2 + 1] + addr[c + 1]);
+            }
+        }
+    }
+}
+
+template <typename T>
+static int launch_ln_indexed(const LnIndexedArgs& a, int D, hipStream_t s) {
+    const dim3 grid((a.rows + 3) / 4), block(256);
+    switch (D) {
+        case 128: hipLaunchKernelGGL((layernorm_indexed_kernel<T, 2>), grid, block, 0, s, a); break;
+        case 256: hipLaunchKernelGGL((layernorm_indexed_kernel<T, 4>), grid, block, 0, s, a); break;
+        case 1024: hipLaunchKernelGGL((layernorm_indexed_kernel<T, 16>), grid, block, 0, s, a); break;
+        default: slime_set_error("layernorm: D=%d unsupported (128, 256, 1024)", D); return SLIME_EINVAL;
+    }
+    SLIME_CHECK_LAUNCH("layernorm_indexed");
+    return SLIME_OK;
+}
+
+// internal (not part of the C ABI)
+int layernorm_crops_indexed_launch(const void* feats, int dtype, int P, const int* table, int n_crops, int D, const float* w, const float* b,
+                                   float eps, void* out_t, void* out_t2, const float* add, int add_period, void* stream) {
+    SLIME_REQUIRE(feats && table && w && b && out_t && P > 0 && n_crops > 0 && (long)n_crops * P < (1L << 31), "layernorm_crops_indexed: bad input");
+    SLIME_REQUIRE(!out_t2 || (add && add_period > 0), "layernorm_crops_indexed: out_t2 needs add/add_period");
+    LnIndexedArgs a{(const char*)feats, table, P, n_crops * P, w, b, eps, out_t, out_t2, add, add_period};
+    if (dtype == SLIME_F16) return launch_ln_indexed<F16>(a, D, (hipStream_t)stream);
+    return launch_ln_indexed<BF16>(a, D, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -440,6 +534,59 @@ int adapter_row_map_launch(int* map, long rows_g, int P, long rows_l, long per_i
     return SLIME_OK;
 }
 
+// Plan of the RAGGED fused adapter (slime_adapter_forward_ragged): every image has its own crop count, grid and first token row
+// (RaggedLayout, by value).  One thread per entry of three int32 tables:
+//   row_map     [B*P + sum n_i*q]  adapter_row_map_kernel's arithmetic with image b's own nw / n / dst0
+//   glob_crops  [B]                index in feats of each image's global crop            (select_crops_indexed_kernel)
+//   local_crops [sum n_i]          index in feats of each local crop, in image order    (layernorm_indexed_kernel)
+// The image of a local row is found by a scan over the prefix array in the kernel arguments (at most 64 steps; the index is per lane, so
+// the reads are vector loads from the argument segment -- no scratch, no table in memory).
+__global__ void __launch_bounds__(256) adapter_ragged_plan_kernel(RaggedLayout L, int* row_map, int* glob_crops, int* local_crops) {
+    const int B = L.n_images;
+    const long rows_g = (long)B * L.P, rows_l = L.lrow0[B], n_loc = rows_l / L.q;
+    long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e < rows_g) {
+        const int b = (int)(e / L.P);
+        row_map[e] = L.dst0[b] + (int)(e % L.P);
+        return;
+    }
+    e -= rows_g;
+    if (e < rows_l) {
+        int b = 0;
+        while (b < B - 1 && e >= L.lrow0[b + 1]) ++b;
+        const long rr = e - L.lrow0[b];
+        long d = rr;
+        if (L.merge) {
+            const int g = L.g, nw = L.nw[b];
+            const int qx = (int)(rr % g), qy = (int)((rr / g) % g), k = (int)(rr / ((long)g * g));
+            const int gx = k % nw, gy = k / nw;
+            d = ((long)(gy * g + qy) * nw + gx) * g + qx;
+        }
+        row_map[rows_g + e] = L.dst0[b] + L.P + (int)d;
+        return;
+    }
+    e -= rows_l;
+    if (e < B) {
+        glob_crops[e] = L.crop0[e];
+        return;
+    }
+    e -= B;
+    if (e < n_loc) {
+        int b = 0;
+        while (b < B - 1 && e * L.q >= L.lrow0[b + 1]) ++b;
+        local_crops[e] = L.crop0[b] + 1 + (int)(e - L.lrow0[b] / L.q);
+    }
+}
+
+int adapter_ragged_plan_launch(const RaggedLayout& L, int* row_map, int* glob_crops, int* local_crops, void* stream) {
+    const int B = L.n_images;
+    const long total = (long)B * L.P + L.lrow0[B] + B + L.lrow0[B] / L.q;
+    hipLaunchKernelGGL(adapter_ragged_plan_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, L, row_map,
+                       glob_crops, local_crops);
+    SLIME_CHECK_LAUNCH("adapter_ragged_plan");
+    return SLIME_OK;
+}
+
 extern "C" int slime_merge_rows(const float* in, void* out, int out_dtype, long dst_row0, int nw, int nh, int g,
                                 int C, int merge, void* stream) {
     return slime_merge_rows_batched(in, 0, out, out_dtype, 0, dst_row0, 1, nw, nh, g, C, merge, stream);
@@ -480,6 +627,40 @@ extern "C" int slime_select_crops(const void* feats, int dtype, int P, int C, in
     if (dtype == SLIME_F16) hipLaunchKernelGGL(select_crops_kernel<F16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)feats, P, C, period, first, per_image, rows, out_f32, (char*)out_t);
     else hipLaunchKernelGGL(select_crops_kernel<BF16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)feats, P, C, period, first, per_image, rows, out_f32, (char*)out_t);
     SLIME_CHECK_LAUNCH("select_crops");
+    return SLIME_OK;
+}
+
+// The same with the source crop of output crop j read from a DEVICE table (ragged fused adapter): crop = table[j].
+template <typename T>
+__global__ void __launch_bounds__(256) select_crops_indexed_kernel(const char* feats, int P, int C, const int* table, long rows,
+                                                                   float* out_f32, char* out_t) {
+    const int lane = threadIdx.x & 63;
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const long j = r / P, i = r % P;
+    const long crop = table[j];
+    const char* src = feats + ((size_t)crop * P + i) * C * 2;
+    for (int c = lane * 8; c < C; c += 512) {
+        const u32x4 v = *reinterpret_cast<const u32x4*>(src + (size_t)c * 2);
+        if (out_t) *reinterpret_cast<u32x4*>(out_t + ((size_t)r * C + c) * 2) = v;
+        if (out_f32) {
+            float* d = out_f32 + (size_t)r * C + c;
+            *reinterpret_cast<float4*>(d) = make_float4(T::lo(v[0]), T::hi(v[0]), T::lo(v[1]), T::hi(v[1]));
+            *reinterpret_cast<float4*>(d + 4) = make_float4(T::lo(v[2]), T::hi(v[2]), T::lo(v[3]), T::hi(v[3]));
+        }
+    }
+}
+
+// internal (not part of the C ABI)
+int select_crops_indexed_launch(const void* feats, int dtype, int P, int C, const int* table, int n_crops, float* out_f32, void* out_t,
+                                void* stream) {
+    SLIME_REQUIRE(feats && table && (out_f32 || out_t) && P > 0 && C % 8 == 0 && n_crops > 0, "select_crops_indexed: bad input");
+    SLIME_REQUIRE(dtype == SLIME_BF16 || dtype == SLIME_F16, "select_crops_indexed: features must be BF16 or F16");
+    const long rows = (long)n_crops * P;
+    dim3 grid((unsigned)((rows + 3) / 4));
+    if (dtype == SLIME_F16) hipLaunchKernelGGL(select_crops_indexed_kernel<F16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)feats, P, C, table, rows, out_f32, (char*)out_t);
+    else hipLaunchKernelGGL(select_crops_indexed_kernel<BF16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)feats, P, C, table, rows, out_f32, (char*)out_t);
+    SLIME_CHECK_LAUNCH("select_crops_indexed");
     return SLIME_OK;
 }
 

@@ -14,8 +14,11 @@ post_qformer + MLP sequence; only the tiny data-dependent tail (merge, router, c
 When every image of the batch has the same crop layout (the usual case: one resolution bucket per batch) the
 whole adapter -- both experts of the GatedBlock, post_qformer, the shared projection MLP over the stacked rows,
 gate mix and spatial merge -- is ONE C-ABI call (``slime_adapter_forward``) on the tower's 16-bit features, as
-in the reference, which hands fp16/bf16 features to its adapter; ragged batches take the per-module sequence,
-where the tower hands over fp32 features.
+in the reference, which hands fp16/bf16 features to its adapter.  A batch whose images have different crop counts or
+grids (the usual anyres batch) takes the same sequence through ``slime_adapter_forward_ragged``: one flat token buffer,
+every image at its own row offset, the router on that buffer directly.  What stays on the per-module sequence, where the
+tower hands over fp32 features: ``images_mask``, ``use_local_only`` / ``use_global_only``, non-gated projectors,
+``fused_adapter=False`` and more than 64 images in one call.
 
 ``SlimeMetaForCausalLM`` can be mixed into an HF causal LM exactly like ``LlavaMetaForCausalLM``
 (INTEGRATION.md); ``SlimeVisualEncoder`` is the standalone form used by bench.py and the tests.
@@ -65,6 +68,28 @@ def _uniform_layout(split_sizes, image_sizes, cfg, crop: int, merge_type: str):
     return (n_local, nw, nh, True) if nw * nh == n_local else None
 
 
+def _ragged_layout(split_sizes, image_sizes, cfg, crop: int, merge_type: str):
+    """Per-image crop grids ``[(nw_i, nh_i)]`` for the ragged fused adapter (``(0, 0)``: an image without local crops; 'flat':
+    ``(n_i, 1)``), or None when it cannot take the batch: 'spatial' without image sizes, a grid that does not match its image's
+    crop count, another merge type, or more images than the call's layout holds."""
+    if not split_sizes or len(split_sizes) > ops.RAGGED_MAX_IMAGES or any(s < 1 for s in split_sizes):
+        return None
+    if merge_type == "flat":
+        return [(s - 1, 1) if s > 1 else (0, 0) for s in split_sizes]
+    if merge_type != "spatial" or image_sizes is None or len(image_sizes) != len(split_sizes):
+        return None
+    grids = []
+    for s, sz in zip(split_sizes, image_sizes):
+        if s == 1:
+            grids.append((0, 0))
+            continue
+        nw, nh = get_anyres_image_grid_shape(sz, cfg.image_grid_pinpoints, crop)
+        if nw * nh != s - 1:
+            return None
+        grids.append((int(nw), int(nh)))
+    return grids
+
+
 def _project_local(projector, comp: torch.Tensor, operand_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """``mm_projector`` on the compressed local crops [sum n_i, g*g, D] of a whole batch.  The reference calls the projector
     per image (n_i <= 7 crops), where GatedBlock.forward's test ``x.shape[0] != 576 and x.shape[1] != 576``
@@ -112,6 +137,16 @@ def _fused_adapter(model, images: torch.Tensor, layout, out_dtype: torch.dtype, 
     post = model.sampler.post_qformer.packed(feats.shape[1], T) if n_local else None
     return ops.adapter_forward(model.mm_projector.packed(T), post, feats, B, n_local, nw, nh, merge,
                                int(model.mm_projector.learnable_gated), out_dtype, out)
+
+
+def _fused_adapter_ragged(model, images: torch.Tensor, grids, merge: bool, out_dtype: torch.dtype):
+    """tower -> slime_adapter_forward_ragged: (flat tokens [sum_i (576 + n_i*g*g), H], first row of every image)."""
+    tower = model.get_vision_tower()
+    T = _operand_dtype(images, model.mm_projector.projection[0].weight)
+    feats = tower(images, out_dtype=T)
+    post = model.sampler.post_qformer.packed(feats.shape[1], T) if feats.shape[0] > len(grids) else None
+    return ops.adapter_forward_ragged(model.mm_projector.packed(T), post, feats, grids, merge,
+                                      int(model.mm_projector.learnable_gated), out_dtype)
 
 
 def _check_token_ids(t, vocab_size):
@@ -247,8 +282,9 @@ class SlimeMetaForCausalLM(ABC):
             text_emb, text_mask = self.get_pure_text_embedding(input_ids, attention_mask, labels)
             B = len(split_sizes)
             layout = None
-            if (getattr(cfg, "fused_adapter", True) and isinstance(model.mm_projector, GatedBlock) and images_mask is None
-                    and not use_local_only and not use_global_only):
+            fusable = (bool(getattr(cfg, "fused_adapter", True)) and isinstance(model.mm_projector, GatedBlock) and images_mask is None
+                       and not use_local_only and not use_global_only)
+            if fusable:
                 layout = _uniform_layout(list(split_sizes), image_sizes, cfg, tower.config.image_size, merge_type)
             if layout is not None and layout[0] > 0:
                 tokens = _fused_adapter(model, images, layout, torch.float32)        # [B, 576 + n*g*g, H] fp32
@@ -262,6 +298,23 @@ class SlimeMetaForCausalLM(ABC):
                 for i in range(B):
                     routed = tokens[i, P:].index_select(0, keeps[i])
                     outs.append(torch.cat([tokens[i, :P], sep32, routed], dim=0).to(out_dtype).unsqueeze(0))
+                return outs, split_sizes
+            grids = None
+            if fusable and layout is None:
+                grids = _ragged_layout(list(split_sizes), image_sizes, cfg, tower.config.image_size, merge_type)
+            if grids is not None:
+                # ragged batch, same program: one flat fp32 token buffer, image i at rows [row0[i], row0[i] + 576 + n_i*g*g); the
+                # router reads its local rows in place (no per-image merge launch, no concatenation)
+                tokens, row0 = _fused_adapter_ragged(model, images, grids, merge_type == "spatial", torch.float32)
+                P, q = tower.num_patches, model.sampler.grid_size ** 2
+                n_rows = [nw * nh * q for nw, nh in grids]
+                sep32 = sep.to(device=tokens.device, dtype=torch.float32).unsqueeze(0)
+                keeps = model.sampler.select_batched(tokens, [r + P for r in row0], n_rows, text_emb, text_mask)
+                outs = []
+                for i in range(B):
+                    glob = tokens[row0[i]:row0[i] + P]
+                    routed = tokens[row0[i] + P:row0[i] + P + n_rows[i]].index_select(0, keeps[i])
+                    outs.append(torch.cat([glob, sep32, routed], dim=0).to(out_dtype).unsqueeze(0))
                 return outs, split_sizes
             feats = tower(images, out_dtype=torch.float32)                      # [sum(1+n_i), 576, D], one batch
             dev = feats.device
@@ -469,6 +522,13 @@ class SlimeVisualEncoder(nn.Module, SlimeMetaForCausalLM):
                 tokens = _fused_adapter(model, images, layout, torch.float32)
                 P = tower.num_patches
                 return [(tokens[i, :P], tokens[i, P:]) for i in range(len(split_sizes))]
+            grids = None
+            if layout is None:
+                grids = _ragged_layout(list(split_sizes), image_sizes, self.config, tower.config.image_size, merge)
+            if grids is not None:
+                tokens, row0 = _fused_adapter_ragged(model, images, grids, merge == "spatial", torch.float32)
+                P, q = tower.num_patches, model.sampler.grid_size ** 2
+                return [(tokens[r:r + P], tokens[r + P:r + P + nw * nh * q]) for r, (nw, nh) in zip(row0, grids)]
         feats = tower(images, out_dtype=torch.float32)
         dev = feats.device
         g_idx, l_idx = _split_indices(split_sizes, dev)

@@ -618,6 +618,86 @@ def adapter_forward(pg: PackedGated, post: Optional["PackedResampler"], feats: t
     return out
 
 
+RAGGED_MAX_IMAGES = 64        # SLIME_ADAPTER_RAGGED_MAX_IMAGES: the per-image layout travels in the plan kernel's arguments
+
+
+def adapter_ragged_plan(grids, P: int, q: int, merge: bool = True, out_row0=None):
+    """Host restatement of the ragged adapter's plan (rowwise.hip: adapter_ragged_plan_kernel), pure integer logic: ``grids`` =
+    per-image ``(nw, nh)`` (``(0, 0)``: no local crops), ``P`` global rows and ``q = g*g`` rows per local crop.  Returns
+    ``(out_row0, rows, row_map)``: the first token-buffer row of every image (packed back to back unless given), the rows a
+    packed buffer needs (the end of the last range when ``out_row0`` is given), and ``row_map(r)`` = token-buffer row of GEMM row
+    r of projection[2]'s output ``[global rows of every image | local rows of every image]``."""
+    n = [int(nw) * int(nh) for nw, nh in grids]
+    if out_row0 is None:
+        out_row0, o = [], 0
+        for n_i in n:
+            out_row0.append(o)
+            o += P + n_i * q
+    out_row0 = [int(r) for r in out_row0]
+    rows = max((r + P + n_i * q for r, n_i in zip(out_row0, n)), default=0)
+    lrow0 = [0]
+    for n_i in n:
+        lrow0.append(lrow0[-1] + n_i * q)
+    B, g = len(n), math.isqrt(q)
+
+    def row_map(r: int) -> int:
+        if r < B * P:
+            return out_row0[r // P] + r % P
+        e = r - B * P
+        b = 0
+        while b < B - 1 and e >= lrow0[b + 1]:
+            b += 1
+        rr = e - lrow0[b]
+        d = rr
+        if merge:
+            nw = max(int(grids[b][0]), 1)
+            qx, qy, k = rr % g, (rr // g) % g, rr // (g * g)
+            gx, gy = k % nw, k // nw
+            d = ((gy * g + qy) * nw + gx) * g + qx
+        return out_row0[b] + P + d
+    return out_row0, rows, row_map
+
+
+def adapter_forward_ragged(pg: PackedGated, post: Optional["PackedResampler"], feats: torch.Tensor, grids, merge: bool = True,
+                           learnable_gated: int = -1, out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None,
+                           out_row0=None):
+    """Fused adapter for images with DIFFERENT crop layouts (``slime_adapter_forward_ragged``): tower features T
+    [sum_i (1 + n_i), 576, D] in image order, ``grids[i] = (nw_i, nh_i)`` with n_i = nw_i * nh_i local crops (``(0, 0)``: none;
+    ``merge=False``: ``(n_i, 1)``).  Returns ``(tokens [rows, H], out_row0)``: image i owns rows ``[out_row0[i], out_row0[i] + 576 +
+    n_i*g*g)`` -- gated global rows, then its local rows in raster order of its own grid.  ``out`` may be a larger flat [rows, H]
+    buffer (fp32 or T) with ``out_row0`` chosen by the caller; rows no image owns are left untouched."""
+    lib = _lib.load()
+    _require_cuda(feats, "feats")
+    if feats.dtype != pg.mlp.dtype:
+        feats = feats.to(pg.mlp.dtype)
+    feats = feats.contiguous()
+    grids = [(int(nw), int(nh)) for nw, nh in grids]
+    B, n_crops = len(grids), sum(1 + nw * nh for nw, nh in grids)
+    if feats.dim() != 3 or feats.shape[0] != n_crops or feats.shape[1] != pg.attn.n_kv or feats.shape[2] != pg.mlp.in_dim:
+        raise _lib.SlimeHipError(f"adapter_forward_ragged: the grids {grids} hold {n_crops} crops of [{pg.attn.n_kv}, {pg.mlp.in_dim}], "
+                                 f"feats is {tuple(feats.shape)}")
+    any_local = n_crops > B
+    if any_local and post is None:
+        raise _lib.SlimeHipError("adapter_forward_ragged: local crops without post_qformer")
+    q = post.n_query if any_local else 1
+    row0, rows, _ = adapter_ragged_plan(grids, pg.attn.n_kv, q, merge, out_row0)
+    if out is None:
+        out = torch.empty((rows, pg.mlp.hidden), dtype=out_dtype or feats.dtype, device=feats.device)
+    assert out.dim() == 2 and out.shape[1] == pg.mlp.hidden and out.is_contiguous()
+    nw_a = (C.c_int * max(B, 1))(*[g[0] for g in grids])
+    nh_a = (C.c_int * max(B, 1))(*[g[1] for g in grids])
+    r0_a = (C.c_longlong * max(B, 1))(*row0) if out_row0 is not None else None
+    pdesc = C.byref(post.desc) if any_local else None
+    need = lib.slime_adapter_ragged_workspace_bytes(C.byref(pg.mlp.desc), C.byref(pg.attn.desc), pdesc, B, nw_a, nh_a)
+    ws = pg.ws.get(max(need, 256), feats.device)
+    base = (ws.data_ptr() + 255) // 256 * 256
+    _lib.check(lib.slime_adapter_forward_ragged(C.byref(pg.mlp.desc), C.byref(pg.attn.desc), pg.w_gate.data_ptr(), int(learnable_gated),
+                                                pdesc, feats.data_ptr(), B, nw_a, nh_a, int(merge), out.data_ptr(), dtype_code(out.dtype),
+                                                r0_a, out.shape[0], base, ws.numel() - (base - ws.data_ptr()), _stream()),
+               "slime_adapter_forward_ragged")
+    return out, row0
+
+
 def adapter_forward_precompressed(pg: PackedGated, glob: torch.Tensor, comp: torch.Tensor, n_images: int, n_local: int, nw: int, nh: int,
                                   merge: bool = True, learnable_gated: int = -1, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """Adapter for the compressed-local exchange (slime_amd.dist.sharded_tower_compressed): ``glob`` T [B, 576, D] tower
