@@ -253,6 +253,39 @@ int slime_tile_normalize_batched(const uint8_t* canvas, int images, long canvas_
                                  int crop, const float* mean3_host, const float* std3_host, void* out,
                                  long out_image_crops, int out_dtype, void* stream);
 
+/* ---- the slicer for a batch of DIFFERENTLY sized images (the usual anyres batch), two launches for the whole batch.  A job is one
+ * Pillow-exact resize of one source image, pasted into a black canvas, cut into crop x crop tiles in row-major order and written as
+ * normalised planar crops -- what slime_resize_bicubic_u8 into a zeroed canvas followed by slime_tile_normalize writes, bit for bit,
+ * without the uint8 canvas in between.  An anyres image is two jobs: its thumbnail (canvas = crop x crop, paste at (0, 0)) and its
+ * local canvas.  Launch 1 is the horizontal pass of every job that runs both passes (into tmp); launch 2 is the vertical pass fused
+ * with paste, tiling and normalisation (pad pixels are (0 - mean) / std).  A pass Pillow skips is skipped: with equal widths launch 2
+ * reads the source, with equal heights it evaluates the horizontal taps itself (the row is final), with both equal it only tiles.
+ *   out: out_dtype (F32 / BF16 / F16) [out_crops, 3, crop, crop]; job j owns crops [first_crop, first_crop + tiles); crops no job owns
+ *        are left untouched.
+ * slime_slice_jobs_plan (host only) fills the last three fields of every job and returns the size of tmp; the caller then copies
+ * the table to the device ONCE and passes both copies: slime_slice_jobs validates jobs_host and launches on jobs_dev -- no upload,
+ * no allocation, capturable.  Every check runs before the first launch.  SLIME_EINVAL, with the limit named: n_jobs outside
+ * 1 .. SLIME_SLICE_MAX_JOBS, a canvas that is not a multiple of crop, a paste rectangle that leaves its canvas, a pass whose sizes
+ * differ without tables or with ksize != slime_resample_ksize, crop ranges that overlap or leave [0, out_crops), a stride smaller
+ * than a row, out_dtype, plan fields that are not what slime_slice_jobs_plan sets; SLIME_EWORKSPACE for a short or misaligned tmp
+ * (16 bytes). */
+typedef struct {
+    const uint8_t* src; long src_stride; int src_h, src_w;     /* DEVICE, packed RGB rows, stride in bytes             */
+    int out_h, out_w;                                          /* == Image.resize((out_w, out_h))                      */
+    int canvas_h, canvas_w, x0, y0;                            /* multiples of crop; paste origin; the rest is (0,0,0) */
+    long first_crop;                                           /* row-major tiles -> crops [first_crop, +tiles) of out */
+    const int* bounds_h; const int* kk_h; int ksize_h;         /* DEVICE tables src_w -> out_w; NULL / 0 if equal      */
+    const int* bounds_v; const int* kk_v; int ksize_v;         /* DEVICE tables src_h -> out_h; NULL / 0 if equal      */
+    long tmp_offset; int h_block0, v_block0;                   /* filled by slime_slice_jobs_plan: byte offset of the [src_h, out_w, 3]
+                                                                * intermediate (both passes only, 16-byte aligned), first workgroup of
+                                                                * the job in launch 1 / launch 2                                       */
+} slime_slice_job;
+#define SLIME_SLICE_MAX_JOBS 128                               /* 64 images, as SLIME_ADAPTER_RAGGED_MAX_IMAGES        */
+int slime_slice_jobs_plan(slime_slice_job* jobs_host, int n_jobs, int crop, size_t* tmp_bytes_host);
+int slime_slice_jobs(const slime_slice_job* jobs_host, const slime_slice_job* jobs_dev, int n_jobs, int crop,
+                     const float* mean3_host, const float* std3_host, void* out, long out_crops, int out_dtype,
+                     uint8_t* tmp, size_t tmp_bytes, void* stream);
+
 /* Text-guided router, scores (TextGuidedRouterCosine.forward, resampler/builder.py:186-201):
  * scores[t] = sum_l mask[l] * cos(img[t], text[l]) (mean over l if mask is NULL); img fp32 [T,H], text fp32
  * [L,H], mask uint8 [L]; ws: L+H+4 floats of scratch. */

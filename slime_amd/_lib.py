@@ -75,6 +75,15 @@ class Probe(C.Structure):
     _fields_ = [("layer", c_int), ("kernel", c_int), ("start", c_void_p), ("stop", c_void_p)]
 
 
+class SliceJob(C.Structure):
+    _fields_ = [("src", c_void_p), ("src_stride", c_long), ("src_h", c_int), ("src_w", c_int), ("out_h", c_int), ("out_w", c_int),
+                ("canvas_h", c_int), ("canvas_w", c_int), ("x0", c_int), ("y0", c_int), ("first_crop", c_long),
+                ("bounds_h", c_void_p), ("kk_h", c_void_p), ("ksize_h", c_int), ("bounds_v", c_void_p), ("kk_v", c_void_p), ("ksize_v", c_int),
+                ("tmp_offset", c_long), ("h_block0", c_int), ("v_block0", c_int)]
+
+
+SLICE_MAX_JOBS = 128
+
 _P = C.POINTER
 _SIGNATURES = {
     "slime_abi_version": (c_int, []),
@@ -111,6 +120,9 @@ _SIGNATURES = {
     "slime_tile_normalize_batched": (c_int, [c_void_p, c_int, c_long, c_int, c_int, c_int, _P(c_float), _P(c_float), c_void_p, c_long,
                                              c_int, c_void_p]),
     "slime_tile_normalize": (c_int, [c_void_p, c_int, c_int, c_int, _P(c_float), _P(c_float), c_void_p, c_int, c_void_p]),
+    "slime_slice_jobs_plan": (c_int, [_P(SliceJob), c_int, c_int, _P(c_size_t)]),
+    "slime_slice_jobs": (c_int, [_P(SliceJob), c_void_p, c_int, c_int, _P(c_float), _P(c_float), c_void_p, c_long, c_int, c_void_p,
+                                 c_size_t, c_void_p]),
     "slime_router_scores": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "slime_router_select": (c_int, [c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "slime_router_batched_workspace_floats": (c_size_t, [c_int, c_int, c_int]),

@@ -7,6 +7,7 @@
 // horizontal pass stages the source span of a 256-pixel output segment in LDS with 16-byte loads.
 #include "common.h"
 #include <math.h>
+#include <stdlib.h>
 
 namespace {
 constexpr int PRECISION_BITS = 32 - 8 - 2;
@@ -29,14 +30,12 @@ __device__ __forceinline__ uint8_t clip8(int acc) {
 // segment needs ([xmin(first), xmin(last)+count(last)) x 3), fetched 16 B per lane; spans that do not fit
 // (extreme down-scales) are read from global memory directly.
 constexpr int SEG = 256, SPAN_BYTES = 48 * 1024;
-__global__ void __launch_bounds__(256) resample_h_kernel(const uint8_t* __restrict__ src, long src_image_stride, long src_stride,
-                                                         int src_w, const uint8_t* src_begin, const uint8_t* src_end,
-                                                         uint8_t* __restrict__ dst, long dst_image_stride, long dst_stride, int out_w,
-                                                         const int* __restrict__ bounds, const int* __restrict__ kk, int ksize) {
-    __shared__ __attribute__((aligned(16))) uint8_t span[SPAN_BYTES];
-    const int y = blockIdx.y, x0 = blockIdx.x * SEG, x1 = min(x0 + SEG, out_w) - 1;
-    const uint8_t* row = src + (size_t)blockIdx.z * src_image_stride + (size_t)y * src_stride;
-    dst += (size_t)blockIdx.z * dst_image_stride;
+// One output segment of one source row (shared by the single-size and the job-table kernel): `row` = the source row, `drow` = the
+// destination row, [src_begin, src_end) = the allocation the 16-byte staging loads must stay inside.
+__device__ __forceinline__ void resample_h_segment(uint8_t* span, const uint8_t* row, const uint8_t* src_begin, const uint8_t* src_end,
+                                                   uint8_t* drow, int x0, int out_w, const int* __restrict__ bounds,
+                                                   const int* __restrict__ kk, int ksize) {
+    const int x1 = min(x0 + SEG, out_w) - 1;
     const int first = bounds[2 * x0], last = bounds[2 * x1] + bounds[2 * x1 + 1];     // source pixels [first, last)
     // stage [g0, g1): g0 = the 16-B aligned address at or below the first needed byte (absolute alignment: rows of
     // a packed RGB image are not 16-B aligned themselves)
@@ -73,8 +72,19 @@ __global__ void __launch_bounds__(256) resample_h_kernel(const uint8_t* __restri
             s0 += p[3 * t] * w; s1 += p[3 * t + 1] * w; s2 += p[3 * t + 2] * w;
         }
     }
-    uint8_t* d = dst + (size_t)y * dst_stride + (size_t)x * 3;
+    uint8_t* d = drow + (size_t)x * 3;
     d[0] = clip8(s0); d[1] = clip8(s1); d[2] = clip8(s2);
+}
+
+__global__ void __launch_bounds__(256) resample_h_kernel(const uint8_t* __restrict__ src, long src_image_stride, long src_stride,
+                                                         int src_w, const uint8_t* src_begin, const uint8_t* src_end,
+                                                         uint8_t* __restrict__ dst, long dst_image_stride, long dst_stride, int out_w,
+                                                         const int* __restrict__ bounds, const int* __restrict__ kk, int ksize) {
+    __shared__ __attribute__((aligned(16))) uint8_t span[SPAN_BYTES];
+    const int y = blockIdx.y;
+    const uint8_t* row = src + (size_t)blockIdx.z * src_image_stride + (size_t)y * src_stride;
+    resample_h_segment(span, row, src_begin, src_end, dst + (size_t)blockIdx.z * dst_image_stride + (size_t)y * dst_stride,
+                       blockIdx.x * SEG, out_w, bounds, kk, ksize);
 }
 
 // Vertical pass: a thread owns 4 consecutive bytes of an output row (x*3+c is just a byte column for this
@@ -109,6 +119,152 @@ __global__ void __launch_bounds__(256) resample_v_kernel(const uint8_t* __restri
 #pragma unroll
     for (int i = 0; i < 4; ++i) if (c + i < row_bytes) d[i] = clip8(s[i]);
 }
+
+// ---- job table (slime_slice_jobs): a whole batch of differently sized images in two launches ----------------------------------------
+template <typename T> __device__ __forceinline__ unsigned short to_t1(float x) {
+    return (unsigned short)(T::pack2(x, 0.f) & 0xffffu);
+}
+
+// The job a workgroup belongs to: the last one whose first workgroup index is <= block (jobs without workgroups in this launch
+// repeat their successor's index, so they are never picked).
+template <bool V> __device__ __forceinline__ int job_of_block(const slime_slice_job* __restrict__ jobs, int n_jobs, int block) {
+    int lo = 0, hi = n_jobs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((V ? jobs[mid].v_block0 : jobs[mid].h_block0) <= block) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// Launch 1: resample_h_kernel for every job that runs both passes, into the job's intermediate [src_h, out_w, 3] at tmp + tmp_offset.
+// The staging loads are bounded by the job's OWN source allocation.
+__global__ void __launch_bounds__(256) slice_h_kernel(const slime_slice_job* __restrict__ jobs, int n_jobs, uint8_t* __restrict__ tmp) {
+    __shared__ __attribute__((aligned(16))) uint8_t span[SPAN_BYTES];
+    const slime_slice_job& J = jobs[job_of_block<false>(jobs, n_jobs, blockIdx.x)];
+    const int segs = (J.out_w + SEG - 1) / SEG, local = blockIdx.x - J.h_block0;
+    const int y = local / segs, x0 = (local % segs) * SEG;
+    const uint8_t* src_end = J.src + (size_t)(J.src_h - 1) * J.src_stride + (size_t)J.src_w * 3;
+    resample_h_segment(span, J.src + (size_t)y * J.src_stride, J.src, src_end, tmp + J.tmp_offset + (size_t)y * J.out_w * 3, x0, J.out_w,
+                       J.bounds_h, J.kk_h, J.ksize_h);
+}
+
+// Launch 2: vertical pass + paste + tile + normalise.  A workgroup owns one canvas row of one tile (the unit of tile_normalize_kernel):
+// a thread produces 4 consecutive bytes of the canvas row -- resample_v_kernel's taps over the intermediate (both passes) or the source
+// (equal widths), a copy (equal heights and widths), the horizontal taps read straight from the source row (equal heights: the row
+// is final, it needs no intermediate), 0 outside the paste rectangle -- into LDS, and the interleaved line leaves as three planar
+// channel rows of normalised values.  4-byte loads only where all 4 bytes lie inside the resized row, so nothing outside the job's
+// allocation is touched.
+template <typename T>
+__global__ void __launch_bounds__(256) slice_v_tile_kernel(const slime_slice_job* __restrict__ jobs, int n_jobs, int crop,
+                                                           const uint8_t* __restrict__ tmp, float3 mean, float3 sd, void* out,
+                                                           int out_dtype) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint8_t* line = reinterpret_cast<uint8_t*>(smem);
+    const slime_slice_job& J = jobs[job_of_block<true>(jobs, n_jobs, blockIdx.x)];
+    const int local = blockIdx.x - J.v_block0, tiles_x = J.canvas_w / crop;
+    const int y = local % crop, tile = local / crop;
+    const int tx = tile % tiles_x, ty = tile / tiles_x;
+    const int oy = ty * crop + y - J.y0;                                   // row of the resized image, if inside [0, out_h)
+    const int row_bytes = J.out_w * 3, seg_bytes = crop * 3;
+    const int sb0 = (tx * crop - J.x0) * 3;                                // byte column of the resized row at the segment's start
+    const bool need_h = J.out_w != J.src_w, need_v = J.out_h != J.src_h;
+    const uint8_t* vsrc = J.src;                                           // the rows the vertical taps (or the copy) read
+    long vstride = J.src_stride;
+    if (need_h && need_v) { vsrc = tmp + J.tmp_offset; vstride = row_bytes; }
+    if (oy >= 0 && oy < J.out_h) {
+        int ymin = oy, cnt = 1;
+        const int* k = nullptr;
+        if (need_v) { ymin = J.bounds_v[2 * oy]; cnt = J.bounds_v[2 * oy + 1]; k = J.kk_v + (size_t)oy * J.ksize_v; }
+        for (int i = threadIdx.x * 4; i < seg_bytes; i += 1024) {
+            const int sb = sb0 + i, nb = min(4, seg_bytes - i);
+            uint8_t r[4] = {0, 0, 0, 0};
+            if (sb + nb > 0 && sb < row_bytes) {
+                const uint8_t* p = vsrc + ((long)ymin * vstride + sb);
+                const bool full = nb == 4 && sb >= 0 && sb + 4 <= row_bytes && ((vstride | (size_t)p) & 3) == 0;
+                if (need_v) {
+                    int s[4];
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) s[b] = 1 << (PRECISION_BITS - 1);
+                    for (int t = 0; t < cnt; ++t, p += vstride) {
+                        const int w = k[t];
+                        if (full) {
+                            const unsigned v = *reinterpret_cast<const unsigned*>(p);
+                            s[0] += (int)(v & 255u) * w; s[1] += (int)((v >> 8) & 255u) * w;
+                            s[2] += (int)((v >> 16) & 255u) * w; s[3] += (int)(v >> 24) * w;
+                        } else {
+#pragma unroll
+                            for (int b = 0; b < 4; ++b) if (b < nb && sb + b >= 0 && sb + b < row_bytes) s[b] += p[b] * w;
+                        }
+                    }
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) if (b < nb && sb + b >= 0 && sb + b < row_bytes) r[b] = clip8(s[b]);
+                } else if (need_h) {
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) {
+                        if (b < nb && sb + b >= 0 && sb + b < row_bytes) {
+                            const int x = (sb + b) / 3, c = (sb + b) % 3;
+                            const int xmin = J.bounds_h[2 * x], n = J.bounds_h[2 * x + 1];
+                            const int* kh = J.kk_h + (size_t)x * J.ksize_h;
+                            const uint8_t* q = J.src + (size_t)oy * J.src_stride + (size_t)xmin * 3 + c;
+                            int acc = 1 << (PRECISION_BITS - 1);
+                            for (int t = 0; t < n; ++t) acc += q[3 * t] * kh[t];
+                            r[b] = clip8(acc);
+                        }
+                    }
+                } else if (full) {
+                    const unsigned v = *reinterpret_cast<const unsigned*>(p);
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) r[b] = (uint8_t)(v >> (8 * b));
+                } else {
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) if (b < nb && sb + b >= 0 && sb + b < row_bytes) r[b] = p[b];
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < 4; ++b) if (b < nb) line[i + b] = r[b];                // nb < 4 only at the end of a line whose crop % 4 != 0
+        }
+    } else {
+        for (int i = threadIdx.x; i < seg_bytes; i += 256) line[i] = 0;
+    }
+    __syncthreads();
+    const float m[3] = {mean.x, mean.y, mean.z}, sdv[3] = {sd.x, sd.y, sd.z};
+    for (int i = threadIdx.x; i < seg_bytes; i += 256) {
+        const int c = i / crop, x = i % crop;
+        // tile_normalize_kernel's expression (HF rescale = float32(float64(u8) * (1/255)), normalise = (x - mean) / std in fp32)
+        const float v = ((float)((double)line[x * 3 + c] * (1.0 / 255.0)) - m[c]) / sdv[c];
+        const size_t o = ((((size_t)J.first_crop + tile) * 3 + c) * crop + y) * crop + x;
+        if (out_dtype == SLIME_F32) reinterpret_cast<float*>(out)[o] = v;
+        else reinterpret_cast<unsigned short*>(out)[o] = to_t1<T>(v);
+    }
+}
+
+// What slime_slice_jobs_plan fills in, computed without touching the table: slime_slice_jobs compares the table against it.
+struct SlicePlan { long tmp_offset[SLIME_SLICE_MAX_JOBS]; int h_block0[SLIME_SLICE_MAX_JOBS], v_block0[SLIME_SLICE_MAX_JOBS];
+                   size_t tmp_bytes; long h_blocks, v_blocks; };
+int slice_plan(const slime_slice_job* jobs, int n_jobs, int crop, SlicePlan* p) {
+    SLIME_REQUIRE(jobs && crop > 0, "slice_jobs: null job table or crop %d", crop);
+    SLIME_REQUIRE(n_jobs >= 1 && n_jobs <= SLIME_SLICE_MAX_JOBS, "slice_jobs: %d jobs (1 .. SLIME_SLICE_MAX_JOBS = %d)", n_jobs, SLIME_SLICE_MAX_JOBS);
+    size_t tmp = 0;
+    long hb = 0, vb = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const slime_slice_job& J = jobs[j];
+        SLIME_REQUIRE(J.src_h > 0 && J.src_w > 0 && J.out_h > 0 && J.out_w > 0, "slice_jobs: job %d: empty image (%dx%d -> %dx%d)", j, J.src_h, J.src_w, J.out_h, J.out_w);
+        SLIME_REQUIRE(J.canvas_h > 0 && J.canvas_w > 0 && J.canvas_h % crop == 0 && J.canvas_w % crop == 0,
+                      "slice_jobs: job %d: canvas %dx%d is not a multiple of crop %d", j, J.canvas_h, J.canvas_w, crop);
+        const bool both = J.out_w != J.src_w && J.out_h != J.src_h;
+        p->tmp_offset[j] = both ? (long)tmp : 0;
+        p->h_block0[j] = (int)hb;
+        p->v_block0[j] = (int)vb;
+        if (both) {
+            tmp += align_up((size_t)J.src_h * J.out_w * 3, 16);
+            hb += (long)((J.out_w + SEG - 1) / SEG) * J.src_h;
+        }
+        vb += (long)J.canvas_h * (J.canvas_w / crop);
+        SLIME_REQUIRE(hb < (1L << 31) && vb < (1L << 31), "slice_jobs: more than 2^31 - 1 workgroups in one launch at job %d", j);
+    }
+    p->tmp_bytes = tmp; p->h_blocks = hb; p->v_blocks = vb;
+    return SLIME_OK;
+}
 }  // namespace
 
 extern "C" int slime_resample_ksize(int in_size, int out_size) {
@@ -127,8 +283,9 @@ extern "C" int slime_resample_coeffs(int in_size, int out_size, int* bounds, int
     const double support = 2.0 * filterscale;
     const int ksize = (int)ceil(support) * 2 + 1;
     const double ss = 1.0 / filterscale;
-    double wbuf[4096];
-    SLIME_REQUIRE(ksize <= 4096, "resample_coeffs: scale %d -> %d too large", in_size, out_size);
+    double wstack[4096];
+    double* wbuf = ksize <= 4096 ? wstack : (double*)malloc((size_t)ksize * sizeof(double));     // a > 1000-fold down-scale
+    SLIME_REQUIRE(wbuf, "resample_coeffs: no memory for %d taps (%d -> %d)", ksize, in_size, out_size);
     for (int xx = 0; xx < out_size; ++xx) {
         const double center = (xx + 0.5) * scale;
         double ww = 0.0;
@@ -151,6 +308,7 @@ extern "C" int slime_resample_coeffs(int in_size, int out_size, int* bounds, int
         bounds[2 * xx] = xmin;
         bounds[2 * xx + 1] = xmax;
     }
+    if (wbuf != wstack) free(wbuf);
     return SLIME_OK;
 }
 
@@ -207,4 +365,65 @@ extern "C" int slime_resize_bicubic_u8(const uint8_t* src, int src_h, int src_w,
                                        size_t tmp_bytes, void* stream) {
     return slime_resize_bicubic_u8_batched(src, 1, 0, src_h, src_w, src_stride, dst, 0, dst_stride, out_h, out_w, bounds_h, kk_h, ksize_h,
                                            bounds_v, kk_v, ksize_v, tmp, tmp_bytes, stream);
+}
+
+extern "C" int slime_slice_jobs_plan(slime_slice_job* jobs, int n_jobs, int crop, size_t* tmp_bytes) {
+    SlicePlan p;
+    SLIME_REQUIRE(tmp_bytes, "slice_jobs_plan: null tmp_bytes");
+    const int rc = slice_plan(jobs, n_jobs, crop, &p);
+    if (rc != SLIME_OK) return rc;
+    for (int j = 0; j < n_jobs; ++j) {
+        jobs[j].tmp_offset = p.tmp_offset[j];
+        jobs[j].h_block0 = p.h_block0[j];
+        jobs[j].v_block0 = p.v_block0[j];
+    }
+    *tmp_bytes = p.tmp_bytes;
+    return SLIME_OK;
+}
+
+extern "C" int slime_slice_jobs(const slime_slice_job* jobs, const slime_slice_job* jobs_dev, int n_jobs, int crop, const float* mean3,
+                                const float* std3, void* out, long out_crops, int out_dtype, uint8_t* tmp, size_t tmp_bytes,
+                                void* stream) {
+    SLIME_REQUIRE(jobs && jobs_dev && out && mean3 && std3, "slice_jobs: null pointer (the job table is given twice: host and device copy)");
+    SLIME_REQUIRE(out_dtype == SLIME_F32 || out_dtype == SLIME_BF16 || out_dtype == SLIME_F16, "slice_jobs: out_dtype %d is not F32 / BF16 / F16", out_dtype);
+    SlicePlan p;
+    const int rc = slice_plan(jobs, n_jobs, crop, &p);
+    if (rc != SLIME_OK) return rc;
+    for (int j = 0; j < n_jobs; ++j) {
+        const slime_slice_job& J = jobs[j];
+        SLIME_REQUIRE(J.src, "slice_jobs: job %d: null source", j);
+        SLIME_REQUIRE(J.src_stride >= (long)J.src_w * 3, "slice_jobs: job %d: row stride %ld smaller than a row of %d bytes", j, J.src_stride, J.src_w * 3);
+        SLIME_REQUIRE(J.x0 >= 0 && J.y0 >= 0 && (long)J.x0 + J.out_w <= J.canvas_w && (long)J.y0 + J.out_h <= J.canvas_h,
+                      "slice_jobs: job %d: paste rectangle %dx%d at (%d, %d) leaves the %dx%d canvas", j, J.out_h, J.out_w, J.x0, J.y0, J.canvas_h, J.canvas_w);
+        SLIME_REQUIRE(J.out_w == J.src_w || (J.bounds_h && J.kk_h && J.ksize_h == slime_resample_ksize(J.src_w, J.out_w)),
+                      "slice_jobs: job %d: horizontal tables missing or ksize %d != %d", j, J.ksize_h, slime_resample_ksize(J.src_w, J.out_w));
+        SLIME_REQUIRE(J.out_h == J.src_h || (J.bounds_v && J.kk_v && J.ksize_v == slime_resample_ksize(J.src_h, J.out_h)),
+                      "slice_jobs: job %d: vertical tables missing or ksize %d != %d", j, J.ksize_v, slime_resample_ksize(J.src_h, J.out_h));
+        const long tiles = (long)(J.canvas_h / crop) * (J.canvas_w / crop);
+        SLIME_REQUIRE(J.first_crop >= 0 && J.first_crop + tiles <= out_crops, "slice_jobs: job %d: crops [%ld, %ld) outside the output's [0, %ld)", j,
+                      J.first_crop, J.first_crop + tiles, out_crops);
+        for (int i = 0; i < j; ++i) {
+            const long ti = (long)(jobs[i].canvas_h / crop) * (jobs[i].canvas_w / crop);
+            SLIME_REQUIRE(J.first_crop >= jobs[i].first_crop + ti || jobs[i].first_crop >= J.first_crop + tiles,
+                          "slice_jobs: crops of jobs %d and %d overlap ([%ld, %ld) and [%ld, %ld))", i, j, jobs[i].first_crop, jobs[i].first_crop + ti,
+                          J.first_crop, J.first_crop + tiles);
+        }
+        SLIME_REQUIRE(J.tmp_offset == p.tmp_offset[j] && J.h_block0 == p.h_block0[j] && J.v_block0 == p.v_block0[j],
+                      "slice_jobs: job %d: tmp_offset / h_block0 / v_block0 are not what slime_slice_jobs_plan sets (plan not run?)", j);
+    }
+    if (p.tmp_bytes && (!tmp || tmp_bytes < p.tmp_bytes || ((size_t)tmp & 15))) {
+        slime_set_error("slice_jobs: tmp needs %zu bytes, 16-byte aligned (got %zu at %p)", p.tmp_bytes, tmp ? tmp_bytes : (size_t)0, (void*)tmp);
+        return SLIME_EWORKSPACE;
+    }
+    if (p.h_blocks) {
+        hipLaunchKernelGGL(slice_h_kernel, dim3((unsigned)p.h_blocks), dim3(256), 0, (hipStream_t)stream, jobs_dev, n_jobs, tmp);
+        SLIME_CHECK_LAUNCH("slice_h");
+    }
+    const float3 mean = make_float3(mean3[0], mean3[1], mean3[2]), sd = make_float3(std3[0], std3[1], std3[2]);
+    const dim3 grid((unsigned)p.v_blocks), block(256);
+    const size_t lds = align_up((size_t)crop * 3, 4);
+    if (out_dtype == SLIME_F16) hipLaunchKernelGGL((slice_v_tile_kernel<F16>), grid, block, lds, (hipStream_t)stream, jobs_dev, n_jobs, crop, tmp, mean, sd, out, out_dtype);
+    else hipLaunchKernelGGL((slice_v_tile_kernel<BF16>), grid, block, lds, (hipStream_t)stream, jobs_dev, n_jobs, crop, tmp, mean, sd, out, out_dtype);
+    SLIME_CHECK_LAUNCH("slice_v_tile");
+    return SLIME_OK;
 }

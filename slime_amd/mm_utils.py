@@ -114,6 +114,20 @@ def process_anyres_image(image: Image.Image, processor, grid_pinpoints) -> torch
     return torch.stack([processor.preprocess(v, return_tensors="pt")["pixel_values"][0] for v in views], dim=0)
 
 
+def anyres_geometry(size: Tuple[int, int], crop: int = CROP) -> Tuple[int, int, int, int, int, int, int]:
+    """Integers of the anyres slicer for an image of ``size`` = (width, height): ``(tw, th, nw, nh, x0, y0, n_local)`` -- the canvas
+    :func:`select_best_resolution_uhd` picks, the resized size and the paste origin of :func:`resize_and_pad_image` on it, and the
+    number of ``crop`` x ``crop`` tiles."""
+    W, H = size
+    tw, th = select_best_resolution_uhd((W, H), (crop, crop))
+    sw, sh = tw / W, th / H
+    if sw < sh:
+        nw, nh = tw, min(math.ceil(H * sw), th)
+    else:
+        nh, nw = th, min(math.ceil(W * sh), tw)
+    return tw, th, nw, nh, (tw - nw) // 2, (th - nh) // 2, (tw // crop) * (th // crop)
+
+
 def slice_image_gpu(image_u8: torch.Tensor, crop: int = CROP) -> Tuple[torch.Tensor, torch.Tensor]:
     """The slicer on the device: uint8 [H, W, 3] image (already in HBM) -> (uint8 [crop, crop, 3] global
     thumbnail, uint8 padded local canvas), bit-identical to :func:`anyres_canvas` -- the uhd grid choice on
@@ -149,6 +163,38 @@ def process_anyres_image_gpu(image, processor, grid_pinpoints, device, dtype=tor
     g = ops.tile_normalize(thumb, crop, processor.image_mean, processor.image_std, dtype)
     l = ops.tile_normalize(canvas, crop, processor.image_mean, processor.image_std, dtype)
     return torch.cat([g, l], dim=0)
+
+
+RAGGED_MAX_IMAGES = 64   # images per slime_slice_jobs call (two jobs each: SLIME_SLICE_MAX_JOBS = 128)
+
+
+def process_images_gpu_ragged(images, image_processor, model_cfg, device, dtype=torch.float32):
+    """The device slicer for a batch of images of ANY sizes (``image_aspect_ratio='anyres'``): images (PIL or uint8 [H, W, 3] tensors,
+    host or device) -> ``(crops, split_sizes, image_sizes)``: crops [sum(1 + n_i), 3, crop, crop] on ``device`` -- image i owns
+    ``split_sizes[i] = 1 + n_i`` consecutive crops, its global view first, bit-identical to :func:`process_anyres_image` --,
+    ``image_sizes[i] = (width, height)``: what ``encode_images`` takes.  Per 64 images two kernel launches and one table upload
+    (``ops.slice_jobs``), whatever the sizes; no uint8 thumbnail or canvas exists in between."""
+    from . import ops
+    mode = getattr(model_cfg, "image_aspect_ratio", None)
+    if mode != "anyres":
+        raise NotImplementedError(f"process_images_gpu_ragged implements image_aspect_ratio='anyres' only (got {mode!r}); "
+                                  "use process_images for the other modes")
+    _parse_pinpoints(model_cfg.image_grid_pinpoints)
+    crop = image_processor.crop_size["height"]
+    arrs = [torch.from_numpy(np.array(im.convert("RGB"))) if isinstance(im, Image.Image) else im for im in images]
+    arrs = [a.to(device, non_blocking=True) for a in arrs]
+    image_sizes = [(int(a.shape[1]), int(a.shape[0])) for a in arrs]
+    geo = [anyres_geometry(s, crop) for s in image_sizes]
+    split_sizes = [1 + g[6] for g in geo]
+    out = torch.empty((sum(split_sizes), 3, crop, crop), dtype=dtype, device=device)
+    jobs, first = [], 0
+    for a, (tw, th, nw, nh, x0, y0, n_local) in zip(arrs, geo):
+        jobs.append((a, crop, crop, crop, crop, 0, 0, first))                # the global thumbnail: aspect NOT preserved
+        jobs.append((a, nw, nh, tw, th, x0, y0, first + 1))                  # the padded local canvas
+        first += 1 + n_local
+    for i in range(0, len(jobs), 2 * RAGGED_MAX_IMAGES):
+        ops.slice_jobs(jobs[i:i + 2 * RAGGED_MAX_IMAGES], crop, image_processor.image_mean, image_processor.image_std, out)
+    return out, split_sizes, image_sizes
 
 
 def process_images_gpu(images, image_processor, model_cfg, device, dtype=torch.float32):
@@ -187,6 +233,12 @@ def process_images_gpu(images, image_processor, model_cfg, device, dtype=torch.f
         ops.tile_normalize_batched(thumbs, crop, image_processor.image_mean, image_processor.image_std, out, 0)
         ops.tile_normalize_batched(canvas, crop, image_processor.image_mean, image_processor.image_std, out, 1)
         return out
+    if len(arrs) > 1:
+        # mixed sizes: the job-table slicer (2 launches for the batch); the per-image tensors are views of its flat crop buffer
+        flat, split, _ = process_images_gpu_ragged(arrs, image_processor, model_cfg, device, dtype)
+        if all(n == split[0] for n in split):
+            return flat.view(len(split), split[0], *flat.shape[1:])
+        return list(flat.split(split, dim=0))
     out = [process_anyres_image_gpu(a, image_processor, model_cfg.image_grid_pinpoints, device, dtype) for a in arrs]
     if all(x.shape == out[0].shape for x in out):
         return torch.stack(out, dim=0)

@@ -841,6 +841,50 @@ def tile_normalize_batched(canvas_u8: torch.Tensor, crop: int, mean, std, out: t
                                                 dtype_code(out.dtype), _stream()), "slime_tile_normalize_batched")
 
 
+def slice_jobs(jobs, crop: int, mean, std, out: torch.Tensor) -> None:
+    """The slicer for differently sized images (``slime_slice_jobs``): two launches and one table upload for the whole list.
+    ``jobs``: up to 128 tuples ``(src, out_w, out_h, canvas_w, canvas_h, x0, y0, first_crop)`` -- ``src`` a uint8 [H, W, 3] device image,
+    resized as ``PIL.Image.resize((out_w, out_h))`` does, pasted at (x0, y0) into a black canvas_h x canvas_w canvas whose row-major
+    ``crop`` x ``crop`` tiles become the normalised crops ``out[first_crop : first_crop + tiles]``.  ``out``: contiguous
+    [crops, 3, crop, crop] device tensor (fp32 / bf16 / fp16); crops no job names keep their contents."""
+    lib = _lib.load()
+    _require_cuda(out, "out")
+    if out.dim() != 4 or tuple(out.shape[1:]) != (3, crop, crop) or not out.is_contiguous():
+        raise ValueError(f"slice_jobs: out must be a contiguous [crops, 3, {crop}, {crop}] tensor, got {tuple(out.shape)}")
+    n = len(jobs)
+    table = (_lib.SliceJob * max(n, 1))()
+    keep = []                                              # tensors the table points to
+    for J, (src, out_w, out_h, canvas_w, canvas_h, x0, y0, first_crop) in zip(table, jobs):
+        _require_cuda(src, "image")
+        if src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 3:
+            raise ValueError(f"slice_jobs expects uint8 [H, W, 3] images, got {src.dtype} {tuple(src.shape)}")
+        if src.stride(2) != 1 or src.stride(1) != 3:
+            src = src.contiguous()
+        keep.append(src)
+        H, W, _ = src.shape
+        J.src, J.src_stride, J.src_h, J.src_w = src.data_ptr(), src.stride(0), H, W
+        J.out_h, J.out_w, J.canvas_h, J.canvas_w, J.x0, J.y0, J.first_crop = out_h, out_w, canvas_h, canvas_w, x0, y0, first_crop
+        if W != out_w:
+            b, k, J.ksize_h = _device_tables(W, out_w, src.device)
+            J.bounds_h, J.kk_h = b.data_ptr(), k.data_ptr()
+            keep += [b, k]
+        if H != out_h:
+            b, k, J.ksize_v = _device_tables(H, out_h, src.device)
+            J.bounds_v, J.kk_v = b.data_ptr(), k.data_ptr()
+            keep += [b, k]
+    tmp_bytes = C.c_size_t(0)
+    _lib.check(lib.slime_slice_jobs_plan(table, n, crop, C.byref(tmp_bytes)), "slime_slice_jobs_plan")
+    nbytes = n * C.sizeof(_lib.SliceJob)
+    staging = torch.empty((nbytes,), dtype=torch.uint8, pin_memory=True)
+    C.memmove(staging.data_ptr(), table, nbytes)
+    table_dev = staging.to(out.device, non_blocking=True)                  # the one upload
+    tmp = torch.empty((tmp_bytes.value,), dtype=torch.uint8, device=out.device) if tmp_bytes.value else None
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s = (C.c_float * 3)(*[float(v) for v in std])
+    _lib.check(lib.slime_slice_jobs(table, table_dev.data_ptr(), n, crop, m, s, out.data_ptr(), out.shape[0], dtype_code(out.dtype),
+                                    _ptr(tmp), tmp_bytes.value, _stream()), "slime_slice_jobs")
+
+
 def router_scores(local_f: torch.Tensor, text: torch.Tensor, mask: Optional[torch.Tensor]) -> torch.Tensor:
     """Cosine router scores [T] (fp32) for local tokens [T,H] against text embeddings [L,H]."""
     lib = _lib.load()
