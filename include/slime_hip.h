@@ -123,6 +123,28 @@ int slime_gemm_pack_b(const void* B, int N, int K, void* out, void* stream);
  * (N % 64 == 0, K % 64 == 0), else 0 (then B is required and B_frag is ignored).  Host-only query. */
 int slime_gemm_b_frag_usable(int N, int K);
 
+/* Opt-in DETERMINISTIC split-K form of slime_gemm_ex, for grids that leave most CUs without a workgroup (tower passes over 1-9
+ * crops).  Two launches ordered by the stream alone (no atomics, no flags, no waiting between workgroups):
+ *   partial   grid = output tiles x splits; workgroup (tile, s) multiplies the 64-wide k-tiles
+ *                 [floor(s nk / splits), floor((s + 1) nk / splits)),  nk = K / 64           (CHUNK RULE: a function of K and splits alone)
+ *             from zero accumulators in the k order of every other kernel, and stores the fp32 accumulators into ws;
+ *   reduce    one workgroup per output tile sums the planes in the fixed order ((p0 + p1) + p2) + ... in fp32  (SUMMATION ORDER)
+ *             and applies the epilogue -- the same code, hence the same arithmetic, as slime_gemm_ex for BIAS_T, BIAS_QUICKGELU_T,
+ *             BIAS_GELU_T, BIAS_F32, BIAS_RESID_F32, BIAS_RESID_F32_LN, BIAS_RESID_T, BIAS_RESID_SPLIT_LN (lo8, stats_out), the
+ *             LayerNorm-fold consumer (ln_stats) and row_map.
+ * A result element depends on (its row of A, B, K, splits) only: bit-identical for any M, any partition of the rows into calls or
+ * rank shards, either tile the library picks and any of the three operand forms (B, B_frag, both); deterministic from run to run.
+ * It is NOT bit-identical to the result of another `splits` (the fp32 sums associate differently); both lie within the same error
+ * bound.  splits in 1..SLIME_GEMM_KSPLIT_MAX and splits <= K / 64; splits == 1 IS slime_gemm_ex (ws may be NULL).
+ * ws: slime_gemm_ksplit_workspace_bytes(M, N, splits) bytes, 256-byte aligned (0 for splits == 1; sized for 128-row tiles:
+ * splits x ceil(M / 128) 128 x N fp32, rounded up to 256); its contents after a call are unspecified.
+ * Every argument of slime_gemm_ex is checked by the same code, and every check precedes the first launch.  SLIME_EINVAL (limit named
+ * in slime_last_error()): splits outside its range, SLIME_EPI_BIAS_GELU_MIX_T (direct-B kernel only), 4 GiB or more of partial
+ * products (the kernels' offsets are 32-bit).  SLIME_EWORKSPACE: ws NULL, short or not 256-byte aligned. */
+#define SLIME_GEMM_KSPLIT_MAX 8
+size_t slime_gemm_ksplit_workspace_bytes(int M, int N, int splits);
+int slime_gemm_ksplit(const slime_gemm_args* args, int splits, void* ws, size_t ws_bytes, void* stream);
+
 /* Name (as rocprofv3 prints it) of the kernel instantiation slime_gemm launches for this shape: host-only query. */
 int slime_gemm_kernel_name(int M, int N, int K, int dtype, int epilogue, int has_b_frag, char* out_host, size_t out_len);
 
@@ -366,6 +388,18 @@ int slime_vit_forward(const slime_vit_desc* d, const void* pixels, int pix_dtype
 int slime_vit_forward_ex(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n_crops,
                          void* out, int out_dtype, int keep_cls, float* hidden_f32,
                          void* ws, size_t ws_bytes, void* stream, const slime_probe* probe);
+
+/* slime_vit_forward with the layer GEMMs optionally run by slime_gemm_ksplit: one `splits` per GEMM of a layer (1 = unsplit, the
+ * launch slime_vit_forward makes).  Off unless asked for; with all four fields 1 the pass is slime_vit_forward's, call for call.
+ * The contract is slime_gemm_ksplit's: for one setting the features are bit-identical however the crops are cut into calls or rank
+ * shards, and they are not bit-identical to another setting's.  Each field must be in its GEMM's range, else SLIME_EINVAL:
+ * qkv, out_proj, fc1 <= hidden / 64, fc2 <= inter / 64, all within 1..SLIME_GEMM_KSPLIT_MAX.
+ * ws: slime_vit_ksplit_workspace_bytes = slime_vit_workspace_bytes + ONE region of partial products sized for the largest of the
+ * four (the launches of a stream are serial). */
+typedef struct { int qkv, out_proj, fc1, fc2; } slime_vit_ksplit;
+size_t slime_vit_ksplit_workspace_bytes(const slime_vit_desc* d, int n_crops, const slime_vit_ksplit* ks);
+int slime_vit_forward_ksplit(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n_crops, void* out, int out_dtype,
+                             int keep_cls, float* hidden_f32, const slime_vit_ksplit* ks, void* ws, size_t ws_bytes, void* stream);
 
 /* All hidden states of ONE pass (HF CLIPVisionModel(..., output_hidden_states=True), which CLIPVisionTower.forward requests,
  * clip_encoder.py:51,55): states_f32 [layers_run + 1, n, 1 + P, hidden] fp32 -- entry 0 = embeddings after pre_layrnorm,

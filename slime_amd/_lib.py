@@ -30,6 +30,8 @@ BF16, F16, F32, U8 = 0, 1, 2, 3
 (EPI_BIAS_T, EPI_BIAS_QUICKGELU_T, EPI_BIAS_GELU_T, EPI_BIAS_F32, EPI_BIAS_RESID_F32, EPI_BIAS_RESID_F32_LN, EPI_BIAS_RESID_T,
  EPI_BIAS_GELU_MIX_T, EPI_BIAS_RESID_SPLIT_LN) = range(9)
 
+GEMM_KSPLIT_MAX = 8        # SLIME_GEMM_KSPLIT_MAX
+
 c_void_p, c_int, c_long, c_float, c_size_t = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
 
 
@@ -71,6 +73,11 @@ class LlamaAttnDesc(C.Structure):
                 ("w_qkv", c_void_p), ("w_o", c_void_p), ("inv_freq", c_void_p), ("w_qkv_frag", c_void_p), ("w_o_frag", c_void_p)]
 
 
+class VitKsplit(C.Structure):
+    """slime_vit_ksplit: splits of the four layer GEMMs for slime_vit_forward_ksplit (1 = unsplit)."""
+    _fields_ = [("qkv", c_int), ("out_proj", c_int), ("fc1", c_int), ("fc2", c_int)]
+
+
 class Probe(C.Structure):
     _fields_ = [("layer", c_int), ("kernel", c_int), ("start", c_void_p), ("stop", c_void_p)]
 
@@ -98,6 +105,8 @@ _SIGNATURES = {
     "slime_patch_embed_prenorm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "slime_gemm_ex": (c_int, [_P(GemmArgs), c_void_p]),
+    "slime_gemm_ksplit_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "slime_gemm_ksplit": (c_int, [_P(GemmArgs), c_int, c_void_p, c_size_t, c_void_p]),
     "slime_attention": (c_int, [c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_void_p, c_long, c_long,
                                 c_void_p, c_long, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "slime_gate_mix": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
@@ -138,6 +147,9 @@ _SIGNATURES = {
     "slime_vit_forward_ex": (c_int, [_P(VitDesc), c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                      c_size_t, c_void_p, _P(Probe)]),
     "slime_vit_forward_states": (c_int, [_P(VitDesc), c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "slime_vit_ksplit_workspace_bytes": (c_size_t, [_P(VitDesc), c_int, _P(VitKsplit)]),
+    "slime_vit_forward_ksplit": (c_int, [_P(VitDesc), c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, _P(VitKsplit), c_void_p,
+                                         c_size_t, c_void_p]),
     "slime_resampler_workspace_bytes": (c_size_t, [_P(ResamplerDesc), c_int]),
     "slime_resampler_forward": (c_int, [_P(ResamplerDesc), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                         c_size_t, c_void_p]),

@@ -137,12 +137,45 @@ static constexpr int g_vit_skip_mask = 0;
     } while (0)
 
 static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out, int out_dtype, int keep_cls,
-                   float* hidden_f32, void* ws, size_t ws_bytes, void* stream, const slime_probe* probe, float* states);
+                   float* hidden_f32, void* ws, size_t ws_bytes, void* stream, const slime_probe* probe, float* states,
+                   const slime_vit_ksplit* ks = nullptr);
 
 extern "C" int slime_vit_forward_ex(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out,
                                     int out_dtype, int keep_cls, float* hidden_f32, void* ws, size_t ws_bytes,
                                     void* stream, const slime_probe* probe) {
     return vit_run(d, pixels, pix_dtype, n, out, out_dtype, keep_cls, hidden_f32, ws, ws_bytes, stream, probe, nullptr);
+}
+
+// splits per layer GEMM (slime_vit_forward_ksplit): each within its GEMM's range -- 1..SLIME_GEMM_KSPLIT_MAX and at most K / 64
+static int vit_ksplit_validate(const slime_vit_desc* d, const slime_vit_ksplit* ks) {
+    const int kmax_d = d->hidden / 64 < SLIME_GEMM_KSPLIT_MAX ? d->hidden / 64 : SLIME_GEMM_KSPLIT_MAX;
+    const int kmax_f = d->inter / 64 < SLIME_GEMM_KSPLIT_MAX ? d->inter / 64 : SLIME_GEMM_KSPLIT_MAX;
+    SLIME_REQUIRE(ks->qkv >= 1 && ks->qkv <= kmax_d, "vit: k-split qkv=%d outside 1..%d (K = hidden = %d)", ks->qkv, kmax_d, d->hidden);
+    SLIME_REQUIRE(ks->out_proj >= 1 && ks->out_proj <= kmax_d, "vit: k-split out_proj=%d outside 1..%d (K = hidden = %d)", ks->out_proj, kmax_d, d->hidden);
+    SLIME_REQUIRE(ks->fc1 >= 1 && ks->fc1 <= kmax_d, "vit: k-split fc1=%d outside 1..%d (K = hidden = %d)", ks->fc1, kmax_d, d->hidden);
+    SLIME_REQUIRE(ks->fc2 >= 1 && ks->fc2 <= kmax_f, "vit: k-split fc2=%d outside 1..%d (K = intermediate = %d)", ks->fc2, kmax_f, d->inter);
+    return SLIME_OK;
+}
+
+static size_t vit_ksplit_partial_bytes(const slime_vit_desc* d, int n, const slime_vit_ksplit* ks) {
+    const int g = d->image / d->patch, M = n * (g * g + 1);
+    size_t b = slime_gemm_ksplit_workspace_bytes(M, 3 * d->hidden, ks->qkv);
+    auto grow = [&](size_t x) { if (x > b) b = x; };
+    grow(slime_gemm_ksplit_workspace_bytes(M, d->hidden, ks->out_proj));
+    grow(slime_gemm_ksplit_workspace_bytes(M, d->inter, ks->fc1));
+    grow(slime_gemm_ksplit_workspace_bytes(M, d->hidden, ks->fc2));
+    return b;
+}
+
+extern "C" size_t slime_vit_ksplit_workspace_bytes(const slime_vit_desc* d, int n_crops, const slime_vit_ksplit* ks) {
+    if (!d || !ks || n_crops <= 0 || d->patch <= 0) return 0;
+    return vit_plan(d, n_crops).total + vit_ksplit_partial_bytes(d, n_crops, ks);
+}
+
+extern "C" int slime_vit_forward_ksplit(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out, int out_dtype,
+                                        int keep_cls, float* hidden_f32, const slime_vit_ksplit* ks, void* ws, size_t ws_bytes, void* stream) {
+    SLIME_REQUIRE(ks, "vit_forward_ksplit: null k-split setting (slime_vit_forward is the unsplit call)");
+    return vit_run(d, pixels, pix_dtype, n, out, out_dtype, keep_cls, hidden_f32, ws, ws_bytes, stream, nullptr, nullptr, ks);
 }
 
 extern "C" int slime_vit_forward_states(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, float* states_f32,
@@ -152,16 +185,25 @@ extern "C" int slime_vit_forward_states(const slime_vit_desc* d, const void* pix
 }
 
 static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out, int out_dtype, int keep_cls,
-                   float* hidden_f32, void* ws, size_t ws_bytes, void* stream, const slime_probe* probe, float* states) {
+                   float* hidden_f32, void* ws, size_t ws_bytes, void* stream, const slime_probe* probe, float* states,
+                   const slime_vit_ksplit* ks) {
     TRY(vit_validate(d));
     SLIME_REQUIRE(pixels && n > 0, "vit: bad input");
     SLIME_REQUIRE(out || hidden_f32 || states, "vit: no output requested");
     SLIME_REQUIRE(!out || out_dtype == SLIME_F32 || is16(out_dtype), "vit: bad out dtype");
+    if (ks) TRY(vit_ksplit_validate(d, ks));
     const VitPlan p = vit_plan(d, n);
-    if (!ws || ws_bytes < p.total || ((uintptr_t)ws % 256) != 0) {
-        slime_set_error("vit: workspace %zu B (need %zu, 256-B aligned)", ws_bytes, p.total);
+    const size_t part_bytes = ks ? vit_ksplit_partial_bytes(d, n, ks) : 0;      // one region of partial products behind the plan
+    if (!ws || ws_bytes < p.total + part_bytes || ((uintptr_t)ws % 256) != 0) {
+        slime_set_error("vit: workspace %zu B (need %zu, 256-B aligned)", ws_bytes, p.total + part_bytes);
         return SLIME_EWORKSPACE;
     }
+    // a layer GEMM: slime_gemm_ex, or the split pair where the caller asked for one (the probe brackets the GEMM as a whole)
+    auto layer_gemm = [&](const slime_gemm_args& a, int splits) {
+        return splits > 1 ? slime_gemm_ksplit(&a, splits, (char*)ws + p.total, part_bytes, stream) : slime_gemm_ex(&a, stream);
+    };
+    const slime_vit_ksplit k1{1, 1, 1, 1};
+    const slime_vit_ksplit& sp = ks ? *ks : k1;
     const int g = d->image / d->patch, P = g * g, S = P + 1, D = d->hidden, F = d->inter;
     const int M = n * S;
     char* w = (char*)ws;
@@ -199,7 +241,7 @@ static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, i
         ga.N = 3 * D; ga.K = D;
         ga.epilogue = SLIME_EPI_BIAS_T; ga.ln_stats = stats; ga.ln_groups = G; ga.ln_colsum = d->colsum_qkv + (size_t)l * 3 * D;
         ga.B_frag = layer_w(d->w_qkv_frag, (size_t)3 * D * D);
-        PROBED(1, slime_gemm_ex(&ga, stream));
+        PROBED(1, layer_gemm(ga, sp.qkv));
         PROBED(2, slime_attention(qkv, (long)S * 3 * D, 3 * D, qkv + (size_t)D * 2, (long)S * 3 * D, 3 * D,
                                   qkv + (size_t)2 * D * 2, (long)S * 3 * D, 3 * D, ctx, (long)S * D, D, n, d->heads, 64, S, S,
                                   dt, stream));
@@ -214,21 +256,21 @@ static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, i
         ga.A = ctx; ga.lda = D; ga.B = layer_w(d->w_o, (size_t)D * D); ga.bias = d->b_o + (size_t)l * D; ga.N = D; ga.K = D;
         resid_update(ga);
         ga.B_frag = layer_w(d->w_o_frag, (size_t)D * D);
-        PROBED(3, slime_gemm_ex(&ga, stream));
+        PROBED(3, layer_gemm(ga, sp.out_proj));
         // ff = quick_gelu(LN2(h) W1^T + b)  (HF :379-380, :346-350)
         ga = slime_gemm_args{};
         ga.M = M; ga.dtype = dt; ga.ln_eps = d->eps;
         ga.A = xn; ga.lda = D; ga.B = layer_w(d->w_fc1, (size_t)F * D); ga.bias = d->b_fc1 + (size_t)l * F; ga.C = ff; ga.ldc = F; ga.N = F; ga.K = D;
         ga.epilogue = SLIME_EPI_BIAS_QUICKGELU_T; ga.ln_stats = stats; ga.ln_groups = G; ga.ln_colsum = d->colsum_fc1 + (size_t)l * F;
         ga.B_frag = layer_w(d->w_fc1_frag, (size_t)F * D);
-        PROBED(5, slime_gemm_ex(&ga, stream));
+        PROBED(5, layer_gemm(ga, sp.fc1));
         // h += ff W2^T + b; prepares the next layer's LN1  (HF :381-383)
         ga = slime_gemm_args{};
         ga.M = M; ga.dtype = dt;
         ga.A = ff; ga.lda = F; ga.B = layer_w(d->w_fc2, (size_t)D * F); ga.bias = d->b_fc2 + (size_t)l * D; ga.N = D; ga.K = F;
         resid_update(ga);
         ga.B_frag = layer_w(d->w_fc2_frag, (size_t)D * F);
-        PROBED(6, slime_gemm_ex(&ga, stream));
+        PROBED(6, layer_gemm(ga, sp.fc2));
         if (states) TRY(snapshot(l + 1));
     }
     if (hidden_f32) TRY(slime_gather_rows_split(xn, lo, dt, S, 0, hidden_f32, SLIME_F32, n, S, D, stream));

@@ -1513,7 +1513,9 @@ extern "C" int slime_gemm_kernel_name(int M, int N, int K, int dtype, int epilog
     return SLIME_OK;
 }
 
-extern "C" int slime_gemm_ex(const slime_gemm_args* a, void* stream) {
+// Argument checks of slime_gemm_ex and slime_gemm_ksplit (one code: both refuse the same calls with the same words), and the kernels'
+// argument block.  Touches no device.
+static int gemm_check_args(const slime_gemm_args* a, GemmArgs& out) {
     SLIME_REQUIRE(a, "gemm: null argument block");
     const int M = a->M, N = a->N, K = a->K, lda = a->lda, ldc = a->ldc;
     SLIME_REQUIRE(a->A && a->C && (a->B || a->B_frag), "gemm: null pointer");
@@ -1559,12 +1561,21 @@ extern "C" int slime_gemm_ex(const slime_gemm_args* a, void* stream) {
 #ifdef SLIME_DIAG
     diag_hook_args(g);
 #endif
+    out = g;
+    return SLIME_OK;
+}
+
+extern "C" int slime_gemm_ex(const slime_gemm_args* a, void* stream) {
+    GemmArgs g;
+    if (const int rc = gemm_check_args(a, g)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (a->dtype == SLIME_BF16) return launch_T<BF16>(g, a->epilogue, s);
     if (a->dtype == SLIME_F16) return launch_T<F16>(g, a->epilogue, s);
     slime_set_error("gemm: dtype %d is not a 16-bit MFMA type", a->dtype);
     return SLIME_EINVAL;
 }
+
+#include "gemm_ksplit.inc"      // slime_gemm_ksplit: the opt-in deterministic split-K pair of launches
 
 extern "C" int slime_gemm_b_frag_usable(int N, int K) { return (N > 0 && K > 0 && N % 64 == 0 && K % 64 == 0) ? 1 : 0; }
 

@@ -87,6 +87,10 @@ class HipCLIPVisionModel(nn.Module):
         # (profiles/r03_stream_split_sweep.txt) -- another tower or device may want another value (SLIME_TOWER_SPLIT_MIN)
         self.split_min_crops = int(os.environ.get("SLIME_TOWER_SPLIT_MIN", "8"))
         self.force_streams = 0                # tools/stream_split_sweep.py: 1 / 2 = override the split policy below
+        # opt-in deterministic split-K of the layer GEMMs (ops.tower_forward k_split): (qkv, out_proj, fc1, fc2) splits or None.
+        # One setting gives the same bits for any crop count and any cut into calls, streams or rank shards; two settings do not
+        # give each other's bits, so every rank of a sharded run sets the same value
+        self.k_split = None
         self._packed: Dict = {}
         self._streams: Optional[List[torch.cuda.Stream]] = None
         self.requires_grad_(False)
@@ -142,8 +146,9 @@ class HipCLIPVisionModel(nn.Module):
         split = self.two_streams and n >= self.split_min_crops
         if self.force_streams:
             split = self.force_streams == 2 and n >= 2
+        ks = {} if self.k_split is None else {"k_split": tuple(self.k_split)}      # None: the call of before, argument for argument
         if not split:
-            return ops.tower_forward(self.packed(select_layer), pixel_values, out_dtype, keep_cls)
+            return ops.tower_forward(self.packed(select_layer), pixel_values, out_dtype, keep_cls, **ks)
         # two independent half batches on two streams: fills each kernel's last partial round.  The first half stays on the CALLER's
         # stream, only the second gets a stream of its own: ROCm maps HIP streams onto 4 hardware queues by default, and with two
         # private tower streams + the caller's + a tail stream + RCCL's, the two halves landed on ONE queue and serialised (round 4:
@@ -157,8 +162,8 @@ class HipCLIPVisionModel(nn.Module):
         out = torch.empty((n, rows, self.config.hidden_size), dtype=out_dtype, device=pixel_values.device)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            ops.tower_forward(self.packed(select_layer, 1), pixel_values[half:], out_dtype, keep_cls, out=out[half:])
-        ops.tower_forward(self.packed(select_layer, 0), pixel_values[:half], out_dtype, keep_cls, out=out[:half])   # both halves land in one tensor
+            ops.tower_forward(self.packed(select_layer, 1), pixel_values[half:], out_dtype, keep_cls, out=out[half:], **ks)
+        ops.tower_forward(self.packed(select_layer, 0), pixel_values[:half], out_dtype, keep_cls, out=out[:half], **ks)   # both halves land in one tensor
         pixel_values.record_stream(side)
         out.record_stream(side)
         cur.wait_stream(side)

@@ -111,12 +111,42 @@ def packed_weight_bytes(*packs) -> int:
     return total
 
 
+_ksplit_ws = Workspace()
+
+
+def _launch_gemm(g: "_lib.GemmArgs", splits: int, device, ws: Optional[torch.Tensor] = None) -> None:
+    """slime_gemm_ex (splits == 1) or slime_gemm_ksplit with a workspace of slime_gemm_ksplit_workspace_bytes (``ws``: a uint8
+    device tensor of the caller's, 256-byte aligned, or the module's grow-only buffer -- ONE per process: calls that may overlap on
+    two streams each pass a ``ws`` of their own)."""
+    lib = _lib.load()
+    if splits == 1:
+        _lib.check(lib.slime_gemm_ex(C.byref(g), _stream()), "slime_gemm_ex")
+        return
+    if ws is None:
+        buf = _ksplit_ws.get(lib.slime_gemm_ksplit_workspace_bytes(g.M, g.N, splits), device)
+        base = (buf.data_ptr() + 255) // 256 * 256
+        nbytes = buf.numel() - (base - buf.data_ptr())
+    else:
+        base, nbytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    _lib.check(lib.slime_gemm_ksplit(C.byref(g), int(splits), base, nbytes, _stream()), "slime_gemm_ksplit")
+
+
+def gemm_ksplit(a: torch.Tensor, w: Optional[torch.Tensor], bias: Optional[torch.Tensor], epilogue: int, splits: int,
+                out: Optional[torch.Tensor] = None, w_frag: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
+                row_map: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``gemm`` as a deterministic split-K pair of launches (slime_gemm_ksplit): K is cut into ``splits`` chunks by a rule of
+    (K, splits) alone and the partial products are summed in plane order, so a result row depends on its row of ``a``, on ``w`` and
+    on ``splits`` only.  splits == 1 is ``gemm``."""
+    return gemm(a, w, bias, epilogue, out, w_frag, resid, row_map, splits=splits, ws=ws)
+
+
 def gemm(a: torch.Tensor, w: Optional[torch.Tensor], bias: Optional[torch.Tensor], epilogue: int,
          out: Optional[torch.Tensor] = None, w_frag: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
-         row_map: Optional[torch.Tensor] = None) -> torch.Tensor:
+         row_map: Optional[torch.Tensor] = None, splits: int = 1, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = epi(a @ w.T + bias); a [M,K] T, w [N,K] T, bias fp32 [N]; w_frag = pack_b_frag(w) (optional); resid T [M,N] for
     EPI_BIAS_RESID_T (out = T(a @ w.T + bias + resid), out may be resid); row_map int32 [M] (device): row r of the result is stored
-    at out[row_map[r]] (``out`` given, with at least max(row_map) + 1 rows; plain T / fp32 epilogues)."""
+    at out[row_map[r]] (``out`` given, with at least max(row_map) + 1 rows; plain T / fp32 epilogues).
+    splits > 1: the deterministic split-K pair of launches (``gemm_ksplit``); ws: its workspace, or None for the module's buffer."""
     lib = _lib.load()
     M, K = a.shape
     if w is None and w_frag is None:
@@ -128,12 +158,12 @@ def gemm(a: torch.Tensor, w: Optional[torch.Tensor], bias: Optional[torch.Tensor
     g = _lib.GemmArgs(A=_ptr(a), lda=a.stride(0), B=_ptr(w), bias=_ptr(bias), C=_ptr(out), ldc=out.stride(0), M=M, N=N, K=K,
                       dtype=dtype_code(a.dtype), epilogue=epilogue, B_frag=_ptr(w_frag), resid=_ptr(resid),
                       ldr=resid.stride(0) if resid is not None else 0, row_map=_ptr(row_map))
-    _lib.check(lib.slime_gemm_ex(C.byref(g), _stream()), "slime_gemm_ex")
+    _launch_gemm(g, splits, a.device, ws)
     return out
 
 
 def gemm_ln_producer(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], h: torch.Tensor,
-                     w_frag: Optional[torch.Tensor] = None):
+                     w_frag: Optional[torch.Tensor] = None, splits: int = 1, ws: Optional[torch.Tensor] = None):
     """h (fp32, in place) += a @ w.T + bias; returns (x16 = T(h), stats [M, N/64, 2]): SLIME_EPI_BIAS_RESID_F32_LN."""
     lib = _lib.load()
     M, K = a.shape
@@ -143,7 +173,7 @@ def gemm_ln_producer(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tens
     g = _lib.GemmArgs(A=_ptr(a), lda=a.stride(0), B=_ptr(w), bias=_ptr(bias), C=_ptr(h), ldc=h.stride(0), M=M, N=N, K=K,
                       dtype=dtype_code(a.dtype), epilogue=_lib.EPI_BIAS_RESID_F32_LN, x16=_ptr(x16), ldx=N, stats_out=_ptr(stats),
                       B_frag=_ptr(w_frag))
-    _lib.check(lib.slime_gemm_ex(C.byref(g), _stream()), "slime_gemm_ex")
+    _launch_gemm(g, splits, a.device, ws)
     return x16, stats
 
 
@@ -171,7 +201,7 @@ def resid_join(hi: torch.Tensor, lo8: torch.Tensor) -> torch.Tensor:
 
 
 def gemm_resid_split(a: torch.Tensor, w: Optional[torch.Tensor], bias: Optional[torch.Tensor], hi: torch.Tensor, lo: torch.Tensor,
-                     w_frag: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     w_frag: Optional[torch.Tensor] = None, splits: int = 1, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """SLIME_EPI_BIAS_RESID_SPLIT_LN on the split residual stream (hi: T [M, N], lo: int8 [M, N], updated in place):
     c = a @ w.T + bias + resid_join(hi, lo); hi, lo = resid_split(c).  Returns stats [M, N/64, 2] (partial sums of c)."""
     assert lo.dtype == torch.int8 and lo.stride(1) == 1, "the stream's lower part is one signed byte per element (ABI 7)"
@@ -182,7 +212,7 @@ def gemm_resid_split(a: torch.Tensor, w: Optional[torch.Tensor], bias: Optional[
     g = _lib.GemmArgs(A=_ptr(a), lda=a.stride(0), B=_ptr(w), bias=_ptr(bias), C=_ptr(hi), ldc=hi.stride(0), M=M, N=N, K=K,
                       dtype=dtype_code(a.dtype), epilogue=_lib.EPI_BIAS_RESID_SPLIT_LN, stats_out=_ptr(stats), B_frag=_ptr(w_frag),
                       lo8=_ptr(lo), ldlo=lo.stride(0))
-    _lib.check(lib.slime_gemm_ex(C.byref(g), _stream()), "slime_gemm_ex")
+    _launch_gemm(g, splits, a.device, ws)
     return stats
 
 
@@ -206,7 +236,8 @@ def patch_embed_prenorm(pixels: torch.Tensor, patch_w_frag: torch.Tensor, cls: t
 
 
 def gemm_ln_consumer(x16: torch.Tensor, stats: torch.Tensor, w_folded: torch.Tensor, bias_folded: torch.Tensor, colsum: torch.Tensor,
-                     eps: float, epilogue: int, w_frag: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     eps: float, epilogue: int, w_frag: Optional[torch.Tensor] = None, splits: int = 1,
+                     ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """epi(LayerNorm(x16) @ W.T + b) with the LayerNorm folded: w_folded = T(W diag(gamma)), bias_folded = b + W beta,
     colsum = row sums of w_folded; stats from the producer.  Output T [M, N]."""
     lib = _lib.load()
@@ -216,7 +247,7 @@ def gemm_ln_consumer(x16: torch.Tensor, stats: torch.Tensor, w_folded: torch.Ten
     g = _lib.GemmArgs(A=_ptr(x16), lda=x16.stride(0), B=_ptr(w_folded), bias=_ptr(bias_folded), C=_ptr(out), ldc=N, M=M, N=N, K=K,
                       dtype=dtype_code(x16.dtype), epilogue=epilogue, ln_stats=_ptr(stats), ln_groups=stats.shape[1],
                       ln_colsum=_ptr(colsum), ln_eps=float(eps), B_frag=_ptr(w_frag))
-    _lib.check(lib.slime_gemm_ex(C.byref(g), _stream()), "slime_gemm_ex")
+    _launch_gemm(g, splits, x16.device, ws)
     return out
 
 
@@ -362,9 +393,13 @@ def pack_tower(state_dict: Dict[str, torch.Tensor], cfg: VisionConfig, dtype: to
 
 
 def tower_forward(pt: PackedTower, pixels: torch.Tensor, out_dtype: Optional[torch.dtype] = None,
-                  keep_cls: bool = False, want_hidden: bool = False, out: Optional[torch.Tensor] = None):
+                  keep_cls: bool = False, want_hidden: bool = False, out: Optional[torch.Tensor] = None,
+                  k_split: Optional[Sequence[int]] = None):
     """pixels [N,3,S,S] (fp32 or the tower dtype) -> features [N, P(+1), D] in out_dtype (written into ``out`` if given:
-    a contiguous [N, P(+1), D] tensor or leading-dim slice of one)."""
+    a contiguous [N, P(+1), D] tensor or leading-dim slice of one).
+    k_split = (qkv, out_proj, fc1, fc2): run those layer GEMMs as deterministic split-K pairs (slime_vit_forward_ksplit; 1 =
+    unsplit).  None (the default) is slime_vit_forward_ex exactly.  For one setting the result does not depend on how the crops are
+    cut into calls; it is not bit-identical to another setting's."""
     lib = _lib.load()
     _require_cuda(pixels, "pixels")
     cfg = pt.cfg
@@ -382,6 +417,19 @@ def tower_forward(pt: PackedTower, pixels: torch.Tensor, out_dtype: Optional[tor
     elif tuple(out.shape) != (n, rows, cfg.hidden_size) or out.dtype != out_dtype or not out.is_contiguous():
         raise ValueError("tower_forward: out must be a contiguous [N, rows, hidden] tensor of the output dtype")
     hidden = torch.empty((n, cfg.seq_len, cfg.hidden_size), dtype=torch.float32, device=pixels.device) if want_hidden else None
+    if k_split is not None:
+        if len(k_split) != 4:
+            raise ValueError("tower_forward: k_split is (qkv, out_proj, fc1, fc2)")
+        if pt.probe is not None:
+            raise ValueError("tower_forward: the timing probe goes with k_split=None (slime_vit_forward_ex)")
+        ks = _lib.VitKsplit(*(int(v) for v in k_split))
+        need = lib.slime_vit_ksplit_workspace_bytes(C.byref(pt.desc), n, C.byref(ks))
+        ws = pt.ws.get(need, pixels.device)
+        base = (ws.data_ptr() + 255) // 256 * 256
+        _lib.check(lib.slime_vit_forward_ksplit(C.byref(pt.desc), pixels.data_ptr(), dtype_code(pixels.dtype), n, out.data_ptr(),
+                                                dtype_code(out_dtype), int(keep_cls), _ptr(hidden), C.byref(ks), base,
+                                                ws.numel() - (base - ws.data_ptr()), _stream()), "slime_vit_forward_ksplit")
+        return (out, hidden) if want_hidden else out
     need = lib.slime_vit_workspace_bytes(C.byref(pt.desc), n)
     ws = pt.ws.get(need, pixels.device)
     base = (ws.data_ptr() + 255) // 256 * 256
