@@ -506,6 +506,28 @@ int slime_adapter_forward_ragged(const slime_mlp_desc* mlp, const slime_resample
 int slime_splice_rows(const void* table, int table_dtype, long table_rows, const void* feats, int feats_dtype,
                       long feat_rows, const int64_t* src, void* out, int out_dtype, long rows, int H, void* stream);
 
+/* The same splice straight from the router's output: the per-image features [global | separator | routed local] are never
+ * built; every output row is resolved on the device from the arrays slime_router_select_batched works on.
+ *   tokens: fp32 [token_rows, H], the fused adapters' token buffer.  Image b's local tokens are rows local_row_off[b] ..
+ *           local_row_off[b] + n_rows[b] - 1, its P global tokens the P rows immediately before them.
+ *   local_row_off [B], n_rows [B], keep_idx [B, T_max], keep_count [B]: the DEVICE arrays of the batched router calls.
+ *   src: DEVICE int64 [rows].  src >= 0: table row; src == -1: zeros; src <= -2: q = -2 - src, image b = q >> 32, position
+ *        p = q & 0xffffffff in that image's feature: p < P token row local_row_off[b] - P + p; p == P table row sep_id;
+ *        p > P token row local_row_off[b] + keep_idx[b * T_max + (p - P - 1)].
+ * Values: a text row as in slime_splice_rows (equal dtypes bit for bit, else a cast); every image-feature row, the separator
+ * included, is out_dtype(mid_dtype(float(source))) -- the value of features rounded to mid_dtype first and spliced afterwards
+ * (mid_dtype == SLIME_F32: no middle rounding).  The output row is zeroed and no source is read when b >= B, p - P - 1 >=
+ * keep_count[b], the keep index lies outside [0, n_rows[b]), the token row lies outside [0, token_rows) or a table id lies
+ * outside the table.  SLIME_EINVAL, limit named: a null pointer; rows, H, B or T_max <= 0; P < 0; sep_id outside the table; a
+ * dtype other than F32 / BF16 / F16; H * sizeof(out element) or H * 4 not a multiple of 16; out, table or tokens not 16-byte
+ * aligned. */
+int slime_splice_routed(const void* table, int table_dtype, long table_rows, long sep_id,
+                        const float* tokens, long token_rows,
+                        const long long* local_row_off, const int* n_rows, int B, int P, int T_max,
+                        const int* keep_idx, const int* keep_count,
+                        int mid_dtype, const int64_t* src, void* out, int out_dtype,
+                        long rows, int H, void* stream);
+
 /* Rotary position embedding, in place, on the first n_rot_heads heads (head_dim 128) of every row of a packed qkv buffer
  * (row stride in elements): HF apply_rotary_pos_emb / rotate_half as called at llama_flash_attn_monkey_patch.py:51-54,
  * angle = (float)pos[row] * inv_freq[i], i < 64 (inv_freq: DEVICE fp32 [64], computed by the host exactly as

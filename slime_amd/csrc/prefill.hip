@@ -5,6 +5,9 @@
 //                            output row is a row of the embedding table, a row of the image features, or zero padding.  The
 //                            index plan is integer host logic (slime_amd/model/llava_arch.py); ALL tensor movement -- what the
 //                            reference does with per-sequence torch.cat / split / stack calls -- is this one launch.
+//   slime_splice_routed      the same rows without the per-image feature tensors in between: an image row names (image, position) and
+//                            is resolved on the device from the batched router's arrays and the fp32 token buffer (opt-in:
+//                            cfg.fused_splice), with the two roundings of the per-image path -- the same bits.
 //   slime_rope               RoPE on the q and k heads of a packed qkv buffer, in place (HF rotate_half convention: pairs
 //                            (i, i + d/2); fp32 cos/sin of pos * inv_freq), q additionally scaled by head_dim^-0.5 * log2 e
 //                            (the attention kernels work in log2 units).
@@ -75,6 +78,115 @@ extern "C" int slime_splice_rows(const void* table, int table_dtype, long table_
                        feats, feats_dtype, reinterpret_cast<const long long*>(src), out, out_dtype, rows, H,
                        table ? table_rows : 0, feats ? feat_rows : 0);
     SLIME_CHECK_LAUNCH("splice_rows");
+    return SLIME_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ routed splice
+// fp32 -> dtype -> fp32: the rounding a tensor.to(dtype) leaves in the value (SLIME_F32: none).
+__device__ __forceinline__ float round_through(float v, int dtype) {
+    if (dtype == SLIME_BF16) return BF16::lo(BF16::pack2(v, 0.f));
+    if (dtype == SLIME_F16) return F16::lo(F16::pack2(v, 0.f));
+    return v;
+}
+__device__ __forceinline__ unsigned pack2_as(float lo, float hi, int dtype) {
+    return dtype == SLIME_BF16 ? BF16::pack2(lo, hi) : F16::pack2(lo, hi);
+}
+
+// One wave per output row, as splice_rows_kernel, but the image-feature rows [glob | sep | routed] are never materialised: the row's
+// source is resolved from the router's device arrays (wave-uniform loads), and an fp32 token row goes to the output through the
+// two roundings of today's tokens.to(images.dtype) -> splice cast, 16 B per lane in, 16 B per lane out.
+//   src >= 0: table row (splice_rows' rule); src == -1: zeros; src <= -2: q = -2 - src, image b = q >> 32, position p = q & 0xffffffff:
+//   p < P global token row local_row_off[b] - P + p; p == P table row sep_id; p > P token row local_row_off[b] + keep_idx[b, p - P - 1].
+// A source that resolves outside its tensor is never dereferenced: the row is zeroed.
+__global__ void __launch_bounds__(256) splice_routed_kernel(const void* table, int table_dtype, long table_rows, long sep_id,
+                                                            const float* tokens, long token_rows, const long long* local_row_off,
+                                                            const int* n_rows, int B, int P, int T_max, const int* keep_idx,
+                                                            const int* keep_count, int mid_dtype, const long long* src, void* out,
+                                                            int out_dtype, long rows, int H) {
+    const int lane = threadIdx.x & 63;
+    const long r = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (r >= rows) return;
+    const long long s = src[r];
+    const int es_out = out_dtype == SLIME_F32 ? 4 : 2;
+    char* o = reinterpret_cast<char*>(out) + (size_t)r * H * es_out;
+    long long trow = -1, krow = -1;                       // table row / token row of this output row; both -1: zeros
+    if (s >= 0) {
+        if (s < table_rows) trow = s;
+    } else if (s <= -2) {
+        const long long q = -2 - s, b = q >> 32, p = q & 0xffffffffLL;
+        if (b < B) {
+            const long long off = local_row_off[b];
+            if (p < P) krow = off - P + p;
+            else if (p == P) trow = sep_id;
+            else {
+                const long long j = p - P - 1;
+                if (j < T_max && j < keep_count[b]) {
+                    const int k = keep_idx[b * T_max + j];
+                    if (k >= 0 && k < n_rows[b]) krow = off + k;
+                }
+            }
+            if (krow >= token_rows) krow = -1;
+        }
+    }
+    if (trow < 0 && krow < 0) {
+        for (int c = lane * 16; c < H * es_out; c += 1024) *reinterpret_cast<u32x4*>(o + c) = u32x4{0u, 0u, 0u, 0u};
+        return;
+    }
+    if (krow >= 0) {                                      // image token: fp32 -> mid -> out
+        const float* t = tokens + (size_t)krow * H;
+        if (out_dtype == SLIME_F32) {
+            for (int c = lane * 4; c < H; c += 256) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(t + c);
+                *reinterpret_cast<f32x4*>(o + (size_t)c * 4) = f32x4{round_through(v[0], mid_dtype), round_through(v[1], mid_dtype),
+                                                                      round_through(v[2], mid_dtype), round_through(v[3], mid_dtype)};
+            }
+            return;
+        }
+        for (int c = lane * 8; c < H; c += 512) {
+            const f32x4 v0 = *reinterpret_cast<const f32x4*>(t + c), v1 = *reinterpret_cast<const f32x4*>(t + c + 4);
+            u32x4 w;
+            w[0] = pack2_as(round_through(v0[0], mid_dtype), round_through(v0[1], mid_dtype), out_dtype);
+            w[1] = pack2_as(round_through(v0[2], mid_dtype), round_through(v0[3], mid_dtype), out_dtype);
+            w[2] = pack2_as(round_through(v1[0], mid_dtype), round_through(v1[1], mid_dtype), out_dtype);
+            w[3] = pack2_as(round_through(v1[2], mid_dtype), round_through(v1[3], mid_dtype), out_dtype);
+            *reinterpret_cast<u32x4*>(o + (size_t)c * 2) = w;
+        }
+        return;
+    }
+    if (s <= -2) {                                        // separator: a table row that takes the image features' two roundings
+        for (int c = lane; c < H; c += 64)
+            store_from_float(out, out_dtype, (size_t)r * H + c, round_through(load_as_float(table, table_dtype, (size_t)trow * H + c), mid_dtype));
+        return;
+    }
+    if (table_dtype == out_dtype) {                       // text token: splice_rows' rule
+        const char* p = reinterpret_cast<const char*>(table) + (size_t)trow * H * es_out;
+        for (int c = lane * 16; c < H * es_out; c += 1024) *reinterpret_cast<u32x4*>(o + c) = *reinterpret_cast<const u32x4*>(p + c);
+        return;
+    }
+    for (int c = lane; c < H; c += 64) store_from_float(out, out_dtype, (size_t)r * H + c, load_as_float(table, table_dtype, (size_t)trow * H + c));
+}
+
+extern "C" int slime_splice_routed(const void* table, int table_dtype, long table_rows, long sep_id, const float* tokens,
+                                   long token_rows, const long long* local_row_off, const int* n_rows, int B, int P, int T_max,
+                                   const int* keep_idx, const int* keep_count, int mid_dtype, const int64_t* src, void* out,
+                                   int out_dtype, long rows, int H, void* stream) {
+    SLIME_REQUIRE(src && out && tokens && table, "splice_routed: null src, out, tokens or table");
+    SLIME_REQUIRE(local_row_off && n_rows && keep_idx && keep_count, "splice_routed: null router state (local_row_off, n_rows, keep_idx, keep_count)");
+    SLIME_REQUIRE(rows > 0 && H > 0 && B > 0 && T_max > 0 && P >= 0, "splice_routed: rows=%ld H=%d B=%d T_max=%d must be positive, P=%d not negative",
+                  rows, H, B, T_max, P);
+    SLIME_REQUIRE(token_rows >= 0, "splice_routed: token_rows=%ld is negative", token_rows);
+    SLIME_REQUIRE(sep_id >= 0 && sep_id < table_rows, "splice_routed: sep_id=%ld outside the table's %ld rows", sep_id, table_rows);
+    auto ok = [](int dt) { return dt == SLIME_F32 || dt == SLIME_BF16 || dt == SLIME_F16; };
+    SLIME_REQUIRE(ok(table_dtype) && ok(mid_dtype) && ok(out_dtype), "splice_routed: bad dtype (table %d, mid %d, out %d: F32, BF16 or F16)",
+                  table_dtype, mid_dtype, out_dtype);
+    SLIME_REQUIRE((H * (out_dtype == SLIME_F32 ? 4 : 2)) % 16 == 0 && (H * 4) % 16 == 0,
+                  "splice_routed: fp32 token rows and output rows must be multiples of 16 bytes (H=%d)", H);
+    SLIME_REQUIRE(((uintptr_t)out % 16) == 0 && ((uintptr_t)table % 16) == 0 && ((uintptr_t)tokens % 16) == 0,
+                  "splice_routed: out, table and tokens must be 16-byte aligned");
+    hipLaunchKernelGGL(splice_routed_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, table, table_dtype,
+                       table_rows, sep_id, tokens, token_rows, local_row_off, n_rows, B, P, T_max, keep_idx, keep_count, mid_dtype,
+                       reinterpret_cast<const long long*>(src), out, out_dtype, rows, H);
+    SLIME_CHECK_LAUNCH("splice_routed");
     return SLIME_OK;
 }
 

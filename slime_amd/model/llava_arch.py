@@ -210,6 +210,49 @@ def splice_plan(input_ids, attention_mask, labels, feat_lens, max_length=None, p
     return src, lab, mask, pos
 
 
+def routed_src(src, feat_lens):
+    """``splice_plan``'s ``src`` for ``ops.splice_routed``: every entry ``-2 - k`` (row k of the virtual concatenation of the per-image
+    features, ``feat_lens[i]`` rows each) becomes ``-2 - (i << 32 | p)``, image i and row p inside its feature; token ids and -1 stay.
+    A zero-row feature owns no k, so it is never named."""
+    import numpy as np
+    src = np.asarray(src, dtype=np.int64)
+    starts = np.concatenate([[0], np.cumsum(np.asarray(feat_lens, dtype=np.int64))]).astype(np.int64)
+    out = src.copy()
+    m = src <= -2
+    k = -2 - src[m]
+    if k.size and int(k.max()) >= int(starts[-1]):
+        raise ValueError("splice plan names a feature row past the last image")
+    img = np.searchsorted(starts, k, side="right") - 1          # the LAST image that starts at or before k: skips zero-row features
+    out[m] = -2 - ((img.astype(np.int64) << 32) | (k - starts[img]))
+    return out
+
+
+def _pure_text_order(ids, padding_side: str = "right", max_len=None):
+    """Column of ``ids`` [B, L] behind every row of get_pure_text_embedding's output, -1 for the zero rows that stand in for the
+    <image> placeholders (appended; prepended for left padding), cut to ``max_len`` (llava_arch.py:162-210).  int64 [B, L']."""
+    import numpy as np
+    ids = np.asarray(ids, dtype=np.int64)
+    rows = []
+    for t in ids:
+        cols = np.nonzero(t != IMAGE_TOKEN_INDEX)[0].astype(np.int64)
+        pad = np.full(t.shape[0] - cols.shape[0], -1, dtype=np.int64)
+        row = np.concatenate([pad, cols]) if padding_side == "left" else np.concatenate([cols, pad])
+        rows.append(row if max_len is None else row[:max_len])
+    return np.stack(rows, 0) if rows else np.zeros((0, 0), dtype=np.int64)
+
+
+def pure_text_plan(ids, padding_side: str = "right", max_len=None):
+    """Source table of ``get_pure_text_embedding`` for one ``ops.splice_rows(table, None, src, dtype)`` launch: int64 [B, L'], a token
+    id per text token (padding ids included, as the reference embeds them), -1 (a zero row) per <image> placeholder."""
+    import numpy as np
+    ids = np.asarray(ids, dtype=np.int64)
+    order = _pure_text_order(ids, padding_side, max_len)
+    return np.where(order >= 0, np.take_along_axis(ids, np.maximum(order, 0), axis=1), -1) if order.size else order
+
+
+_SPLICE_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
 class SlimeMetaModel:
     """Mixin: builds the three hot-path plugins from the config (llava_arch.py:28-44)."""
 
@@ -261,6 +304,68 @@ class SlimeMetaForCausalLM(ABC):
         assert masks.shape == embs.shape[:2]
         return embs, masks
 
+    def _pure_text_planned(self, input_ids, attention_mask):
+        """``get_pure_text_embedding`` as an integer plan on the host and ONE launch (``pure_text_plan`` + ``slime_splice_rows``), for
+        the routed path: fp32 embeddings (the router computes in fp32; widening a 16-bit table row is exact) and the mask, both
+        on the table's device."""
+        import numpy as np
+        table = self.get_model().embed_tokens.weight.detach()
+        ids = input_ids.detach().cpu().numpy().astype(np.int64)
+        _check_token_ids(ids.reshape(-1), table.shape[0])                    # what nn.Embedding would raise on
+        side = getattr(self.config, "tokenizer_padding_side", "right")
+        max_len = getattr(self.config, "tokenizer_model_max_length", None)
+        order = _pure_text_order(ids, side, max_len)
+        src = pure_text_plan(ids, side, max_len)
+        am = np.ones_like(ids) if attention_mask is None else attention_mask.detach().cpu().numpy()
+        mask = np.where(order >= 0, np.take_along_axis(am, np.maximum(order, 0), axis=1), 0)
+        B, L = src.shape
+        emb = ops.splice_rows(table, None, torch.from_numpy(src).reshape(-1).to(table.device), torch.float32).view(B, L, -1)
+        return emb, torch.from_numpy(mask).to(table.device)
+
+    def _splice_routable(self, images) -> bool:
+        """``cfg.fused_splice`` asks for it and ``slime_splice_routed`` can take the call: a table and images of a type it converts,
+        table and tokens on one device."""
+        table = self.get_model().embed_tokens.weight
+        return (bool(getattr(self.config, "fused_splice", False)) and table.dtype in _SPLICE_DTYPES and images.dtype in _SPLICE_DTYPES
+                and table.device == images.device)
+
+    def _fused_route(self, images, input_ids, split_sizes, attention_mask, images_mask, image_sizes, labels, routable: bool):
+        """Tower, fused adapter and batched router for the batches a fused adapter call takes (uniform or ragged crop layouts), else
+        None -- decided on the host, before any device work.  Returns ``(tokens2d, local_row_off, n_rows, P, router_state,
+        counts)``: the flat fp32 token buffer [rows, H]; image i's local tokens are rows ``local_row_off[i] .. + n_rows[i]``, its
+        ``P`` global tokens the rows right before them; the router's device arrays; the kept counts on the host (the step's one
+        D2H read).  ``routable``: the text embeddings for the router come from ``_pure_text_planned``."""
+        model = self.get_model()
+        tower = model.get_vision_tower()
+        cfg = self.config
+        merge_type = getattr(cfg, "mm_patch_merge_type", "flat")
+        fusable = (bool(getattr(cfg, "fused_adapter", True)) and isinstance(model.mm_projector, GatedBlock) and images_mask is None
+                   and not getattr(cfg, "use_local_only", False) and not getattr(cfg, "use_global_only", False))
+        if not fusable:
+            return None
+        layout = _uniform_layout(list(split_sizes), image_sizes, cfg, tower.config.image_size, merge_type)
+        grids = None
+        if layout is None:
+            grids = _ragged_layout(list(split_sizes), image_sizes, cfg, tower.config.image_size, merge_type)
+        if grids is None and (layout is None or layout[0] == 0):
+            return None
+        text_emb, text_mask = self._pure_text_planned(input_ids, attention_mask) if routable \
+            else self.get_pure_text_embedding(input_ids, attention_mask, labels)
+        B, P = len(split_sizes), tower.num_patches
+        if grids is None:
+            tokens = _fused_adapter(model, images, layout, torch.float32)        # [B, 576 + n*g*g, H] fp32
+            rows = tokens.shape[1]
+            tokens, off, n_rows = tokens.view(B * rows, -1), [i * rows + P for i in range(B)], [rows - P] * B
+        else:
+            # ragged batch, same program: one flat fp32 token buffer, image i at rows [row0[i], row0[i] + 576 + n_i*g*g); the
+            # router reads its local rows in place (no per-image merge launch, no concatenation)
+            tokens, row0 = _fused_adapter_ragged(model, images, grids, merge_type == "spatial", torch.float32)
+            q = model.sampler.grid_size ** 2
+            off, n_rows = [r + P for r in row0], [nw * nh * q for nw, nh in grids]
+        # router: all B images in one launch pair, one D2H for the B kept counts (the reference syncs per image)
+        st = model.sampler.select_batched_device(tokens, off, n_rows, text_emb, text_mask)
+        return tokens, off, n_rows, P, st, st.counts
+
     # ------------------------------------------------------------------ the hot path
     def encode_images(self, images, input_ids=None, split_sizes=None, attention_mask=None, images_mask=None,
                       image_sizes=None, labels=None):
@@ -278,44 +383,30 @@ class SlimeMetaForCausalLM(ABC):
         out_dtype = images.dtype
 
         if model.has_sampler and split_sizes is not None:
-            sep = model.embed_tokens(torch.tensor(cfg.seperator, dtype=input_ids.dtype, device=input_ids.device))
-            text_emb, text_mask = self.get_pure_text_embedding(input_ids, attention_mask, labels)
             B = len(split_sizes)
-            layout = None
-            fusable = (bool(getattr(cfg, "fused_adapter", True)) and isinstance(model.mm_projector, GatedBlock) and images_mask is None
-                       and not use_local_only and not use_global_only)
-            if fusable:
-                layout = _uniform_layout(list(split_sizes), image_sizes, cfg, tower.config.image_size, merge_type)
-            if layout is not None and layout[0] > 0:
-                tokens = _fused_adapter(model, images, layout, torch.float32)        # [B, 576 + n*g*g, H] fp32
-                P = tower.num_patches
+            routable = self._splice_routable(images)
+            fused = self._fused_route(images, input_ids, split_sizes, attention_mask, images_mask, image_sizes, labels, routable)
+            if fused is not None and routable:
+                # one launch writes every image's [glob | sep | routed] rows into one flat buffer; the per-image tensors are views
+                tokens, off, n_rows, P, st, counts = fused
+                import numpy as np
+                lens = [P + 1 + c for c in counts]
+                src = np.concatenate([-2 - ((np.int64(i) << 32) | np.arange(n, dtype=np.int64)) for i, n in enumerate(lens)])
+                flat = ops.splice_routed(model.embed_tokens.weight.detach(), int(cfg.seperator), tokens, P, st,
+                                         torch.from_numpy(src).to(tokens.device), out_dtype, out_dtype)
+                return [f.unsqueeze(0) for f in torch.split(flat, lens, dim=0)], split_sizes
+            if fused is not None:
+                tokens, off, n_rows, P, st, counts = fused
+                sep = model.embed_tokens(torch.tensor(cfg.seperator, dtype=input_ids.dtype, device=input_ids.device))
                 sep32 = sep.to(device=tokens.device, dtype=torch.float32).unsqueeze(0)
-                rows = tokens.shape[1]
-                # router: all B images in one launch pair, one D2H for the B kept counts (the reference syncs per image)
-                keeps = model.sampler.select_batched(tokens.view(B * rows, -1), [i * rows + P for i in range(B)], [rows - P] * B,
-                                                     text_emb, text_mask)
                 outs = []
                 for i in range(B):
-                    routed = tokens[i, P:].index_select(0, keeps[i])
-                    outs.append(torch.cat([tokens[i, :P], sep32, routed], dim=0).to(out_dtype).unsqueeze(0))
-                return outs, split_sizes
-            grids = None
-            if fusable and layout is None:
-                grids = _ragged_layout(list(split_sizes), image_sizes, cfg, tower.config.image_size, merge_type)
-            if grids is not None:
-                # ragged batch, same program: one flat fp32 token buffer, image i at rows [row0[i], row0[i] + 576 + n_i*g*g); the
-                # router reads its local rows in place (no per-image merge launch, no concatenation)
-                tokens, row0 = _fused_adapter_ragged(model, images, grids, merge_type == "spatial", torch.float32)
-                P, q = tower.num_patches, model.sampler.grid_size ** 2
-                n_rows = [nw * nh * q for nw, nh in grids]
-                sep32 = sep.to(device=tokens.device, dtype=torch.float32).unsqueeze(0)
-                keeps = model.sampler.select_batched(tokens, [r + P for r in row0], n_rows, text_emb, text_mask)
-                outs = []
-                for i in range(B):
-                    glob = tokens[row0[i]:row0[i] + P]
-                    routed = tokens[row0[i] + P:row0[i] + P + n_rows[i]].index_select(0, keeps[i])
+                    glob = tokens[off[i] - P:off[i]]
+                    routed = tokens[off[i]:off[i] + n_rows[i]].index_select(0, st.keep[i, :counts[i]].long())
                     outs.append(torch.cat([glob, sep32, routed], dim=0).to(out_dtype).unsqueeze(0))
                 return outs, split_sizes
+            sep = model.embed_tokens(torch.tensor(cfg.seperator, dtype=input_ids.dtype, device=input_ids.device))
+            text_emb, text_mask = self.get_pure_text_embedding(input_ids, attention_mask, labels)
             feats = tower(images, out_dtype=torch.float32)                      # [sum(1+n_i), 576, D], one batch
             dev = feats.device
             g_idx, l_idx = _split_indices(split_sizes, dev)
@@ -405,13 +496,21 @@ class SlimeMetaForCausalLM(ABC):
         vocab = self.get_model().embed_tokens.weight.shape[0]
         if getattr(self.get_model(), "has_sampler", False) and ids_np.size:
             _check_token_ids(ids_np.reshape(-1), vocab)
+        routed = None
         if type(images) is list or images.ndim == 5:
             if type(images) is list:
                 images = [x.unsqueeze(0) if x.ndim == 3 else x for x in images]
             concat_images = torch.cat([im for im in images], dim=0)
             split_sizes = [im.shape[0] for im in images]
-            feats, split_sizes = self.encode_images(concat_images, input_ids, split_sizes, attention_mask, images_mask, image_sizes,
-                                                    labels=labels)
+            if getattr(self.get_model(), "has_sampler", False) and self._splice_routable(concat_images):
+                # cfg.fused_splice: no per-image feature tensors -- the router's device arrays go to the splice launch below
+                _require_inference(self.get_model())
+                with torch.no_grad():
+                    routed = self._fused_route(concat_images, input_ids, split_sizes, attention_mask, images_mask, image_sizes, labels, True)
+            feats = []
+            if routed is None:
+                feats, split_sizes = self.encode_images(concat_images, input_ids, split_sizes, attention_mask, images_mask, image_sizes,
+                                                        labels=labels)
             if type(feats) is not list:
                 feats = list(torch.split(feats, split_sizes, dim=0))
             flat = []
@@ -435,15 +534,24 @@ class SlimeMetaForCausalLM(ABC):
         embed = self.get_model().embed_tokens
         table = embed.weight
         dev = table.device
+        feat_lens = [f.shape[0] for f in feats] if routed is None else [routed[3] + 1 + c for c in routed[5]]
         src, lab, mask, pos = splice_plan(ids_np,
                                           None if attention_mask is None else attention_mask.detach().cpu().numpy(),
                                           None if labels is None else labels.detach().cpu().numpy(),
-                                          [f.shape[0] for f in feats], getattr(self.config, "tokenizer_model_max_length", None),
+                                          feat_lens, getattr(self.config, "tokenizer_model_max_length", None),
                                           getattr(self.config, "tokenizer_padding_side", "right"), vocab_size=vocab)
         B, T = src.shape
-        allf = torch.cat([f.reshape(-1, f.shape[-1]) for f in feats], 0).to(dev) if feats else None
         out_dtype = table.dtype if table.dtype in (torch.float32, torch.bfloat16, torch.float16) else torch.float32
-        new_input_embeds = ops.splice_rows(table.detach(), allf, torch.from_numpy(src).reshape(-1).to(dev), out_dtype).view(B, T, -1)
+        if routed is not None:
+            # the same plan with (image, position) in place of rows of a concatenation that is never built; the image rows take
+            # the rounding to the images' dtype that encode_images gives its features, then the cast to the table's
+            tokens, _, _, P, st, _ = routed
+            src_d = torch.from_numpy(routed_src(src, feat_lens)).reshape(-1).to(dev)
+            new_input_embeds = ops.splice_routed(table.detach(), int(self.config.seperator), tokens, P, st, src_d, concat_images.dtype,
+                                                 out_dtype).view(B, T, -1)
+        else:
+            allf = torch.cat([f.reshape(-1, f.shape[-1]) for f in feats], 0).to(dev) if feats else None
+            new_input_embeds = ops.splice_rows(table.detach(), allf, torch.from_numpy(src).reshape(-1).to(dev), out_dtype).view(B, T, -1)
         new_labels = None if labels is None else torch.from_numpy(lab).to(labels.device, labels.dtype)
         new_mask = None if attention_mask is None else torch.from_numpy(mask).to(attention_mask.device, attention_mask.dtype)
         new_pos = None if position_ids is None else torch.from_numpy(pos).to(position_ids.device, position_ids.dtype)
@@ -465,7 +573,8 @@ def default_slime_config(vision_tower: str = "synthetic:1234", hidden_size: int 
              mm_patch_merge_type="spatial", image_aspect_ratio="anyres", mm_resampler_type="cosine",
              mm_resampler_topp=0.95, mm_resampler_dim=144, mm_resampler_temp=1.0, mm_learnable_gated=-1,
              image_grid_pinpoints="[(336, 672), (672, 336), (672, 672), (1008, 336), (336, 1008)]",
-             seperator=1919, pad_token_id=0, use_local_only=False, use_global_only=False)
+             seperator=1919, pad_token_id=0, use_local_only=False, use_global_only=False,
+             fused_splice=False)          # opt-in: router output -> embeddings in one launch (slime_splice_routed), bit-identical
     d.update(over)
     return _Cfg(**d)
 

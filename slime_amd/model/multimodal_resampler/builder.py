@@ -43,6 +43,11 @@ class TextGuidedSampler(nn.Module):
         local-token indices, ascending.  Same per-image arithmetic as ``forward``."""
         return ops.router_topp_batched(tokens, row_off, n_rows, text_embedding, attn_mask, float(self.topp), float(self.temp))
 
+    @torch.no_grad()
+    def select_batched_device(self, tokens, row_off, n_rows, text_embedding, attn_mask=None):
+        """``select_batched`` with the kept indices left on the device (``ops.RouterState``; its ``counts`` are on the host)."""
+        return ops.router_select_batched_device(tokens, row_off, n_rows, text_embedding, attn_mask, float(self.topp), float(self.temp))
+
 
 def build_vision_sampler(config, delay_load=False, **kwargs):
     mm_resampler_type = getattr(config, "mm_resampler_type", None)

@@ -13,7 +13,7 @@ import os
 import threading
 import weakref
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import torch
 import torch.nn.functional as F
@@ -970,20 +970,33 @@ def router_topp(local_f: torch.Tensor, text: torch.Tensor, mask: Optional[torch.
     return keep[: int(cnt.item())].long()
 
 
-def router_topp_batched(tokens: torch.Tensor, row_off: Sequence[int], n_rows: Sequence[int], text: torch.Tensor,
-                        mask: Optional[torch.Tensor], topp: float, temp: float) -> List[torch.Tensor]:
-    """The router for the B images of a step in ONE launch pair and ONE D2H read (of the B kept counts).
+class RouterState(NamedTuple):
+    """What the batched router leaves on the device, plus the one thing the host needs: ``keep`` int32 [B, T_max] (row b: the kept
+    local indices, ascending, in its first ``counts[b]`` entries), ``cnt`` int32 [B], ``off`` int64 [B] (first local row of
+    every image in the token buffer), ``n_rows`` int32 [B]; ``counts`` = ``cnt`` on the host."""
+    keep: torch.Tensor
+    cnt: torch.Tensor
+    off: torch.Tensor
+    n_rows: torch.Tensor
+    counts: List[int]
+
+
+def router_select_batched_device(tokens: torch.Tensor, row_off: Sequence[int], n_rows: Sequence[int], text: torch.Tensor,
+                                 mask: Optional[torch.Tensor], topp: float, temp: float) -> RouterState:
+    """The router for the B images of a step in ONE launch pair and ONE D2H read (of the B kept counts), its results left on the
+    device (``RouterState``) for ``splice_routed``.
     ``tokens`` fp32 [rows, H] (any 2-D contiguous view of the token buffer); image b owns rows
-    ``row_off[b] .. row_off[b] + n_rows[b] - 1``; ``text`` [B, L, H], ``mask`` [B, L] or None.
-    Returns per image the kept LOCAL indices (ascending, int64, relative to row_off[b])."""
+    ``row_off[b] .. row_off[b] + n_rows[b] - 1``; ``text`` [B, L, H], ``mask`` [B, L] or None."""
     lib = _lib.load()
     _require_cuda(tokens, "tokens")
     assert tokens.dim() == 2 and tokens.dtype == torch.float32 and tokens.is_contiguous()
     B, H = len(n_rows), tokens.shape[1]
     dev = tokens.device
     T_max = max(int(n) for n in n_rows) if B else 0
-    if B == 0 or T_max == 0:
-        return [torch.zeros((0,), dtype=torch.long, device=dev) for _ in range(B)]
+    if B == 0 or T_max == 0:                                        # nothing to route: no launch, no sync
+        return RouterState(torch.zeros((B, 1), dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev),
+                           torch.tensor([int(o) for o in row_off], dtype=torch.int64).to(dev),
+                           torch.zeros((B,), dtype=torch.int32, device=dev), [0] * B)
     txt = text.to(device=dev, dtype=torch.float32).contiguous()
     L = txt.shape[1]
     m = None if mask is None else mask.to(device=dev).ne(0).to(torch.uint8).contiguous()
@@ -997,8 +1010,15 @@ def router_topp_batched(tokens: torch.Tensor, row_off: Sequence[int], n_rows: Se
                                                _ptr(m), H, scores.data_ptr(), ws.data_ptr(), _stream()), "slime_router_scores_batched")
     _lib.check(lib.slime_router_select_batched(scores.data_ptr(), cnt_in.data_ptr(), B, T_max, float(temp), float(topp),
                                                keep.data_ptr(), cnt.data_ptr(), _stream()), "slime_router_select_batched")
-    counts = cnt.cpu().tolist()                                   # the step's only host sync
-    return [keep[b, :counts[b]].long() for b in range(B)]
+    return RouterState(keep, cnt, off, cnt_in, cnt.cpu().tolist())           # the step's only host sync
+
+
+def router_topp_batched(tokens: torch.Tensor, row_off: Sequence[int], n_rows: Sequence[int], text: torch.Tensor,
+                        mask: Optional[torch.Tensor], topp: float, temp: float) -> List[torch.Tensor]:
+    """``router_select_batched_device`` as per-image tensors: the kept LOCAL indices of every image (ascending, int64, relative to
+    row_off[b])."""
+    st = router_select_batched_device(tokens, row_off, n_rows, text, mask, topp, temp)
+    return [st.keep[b, :st.counts[b]].long() for b in range(len(n_rows))]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1019,6 +1039,31 @@ def splice_rows(table: Optional[torch.Tensor], feats: Optional[torch.Tensor], sr
                                      _ptr(f), dtype_code(f.dtype) if f is not None else 0, 0 if f is None else f.shape[0],
                                      _ptr(src.contiguous()), out.data_ptr(), dtype_code(out_dtype), rows, H, _stream()),
                "slime_splice_rows")
+    return out
+
+
+def splice_routed(table: torch.Tensor, sep_id: int, tokens: torch.Tensor, P: int, router_state: RouterState, src: torch.Tensor,
+                  mid_dtype: torch.dtype, out_dtype: torch.dtype) -> torch.Tensor:
+    """``splice_rows`` without the per-image features: a ``src`` entry <= -2 names (image b, position p) of the feature
+    ``[P global tokens | table[sep_id] | routed local tokens]`` (``-2 - (b << 32 | p)``, llava_arch.routed_src) and is resolved on the
+    device from ``router_state`` and the fp32 token buffer ``tokens`` [rows, H]; feature rows take the value
+    ``x.to(mid_dtype).to(out_dtype)``.  One launch; returns [src.numel(), H] of ``out_dtype``."""
+    lib = _lib.load()
+    _require_cuda(src, "src")
+    _require_cuda(tokens, "tokens")
+    assert tokens.dim() == 2 and tokens.dtype == torch.float32 and tokens.is_contiguous()
+    assert table.device == tokens.device == src.device, "splice_routed: table, tokens and src live on one device"
+    st = router_state
+    B, T_max = st.keep.shape
+    H = tokens.shape[1]
+    assert table.shape[-1] == H, f"embedding rows of {table.shape[-1]}, token rows of {H}"
+    rows = src.numel()
+    out = torch.empty((rows, H), dtype=out_dtype, device=src.device)
+    t = table.contiguous()
+    _lib.check(lib.slime_splice_routed(_ptr(t), dtype_code(t.dtype), t.shape[0], int(sep_id), tokens.data_ptr(), tokens.shape[0],
+                                       _ptr(st.off), _ptr(st.n_rows), B, int(P), T_max, _ptr(st.keep), _ptr(st.cnt),
+                                       dtype_code(mid_dtype), _ptr(src.contiguous()), out.data_ptr(), dtype_code(out_dtype), rows, H,
+                                       _stream()), "slime_splice_routed")
     return out
 
 
