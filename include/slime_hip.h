@@ -308,6 +308,58 @@ int slime_slice_jobs(const slime_slice_job* jobs_host, const slime_slice_job* jo
                      const float* mean3_host, const float* std3_host, void* out, long out_crops, int out_dtype,
                      uint8_t* tmp, size_t tmp_bytes, void* stream);
 
+/* ---- the "view job" slicer: the other image_aspect_ratio modes of process_images ('pad', 'pad_then_devide', 'any_res', the bare
+ * processor) on the device, in the same two launches per batch.  Where a slice job pastes a resized image into a black canvas and
+ * tiles it, a view job pads FIRST (expand2square: a box of the image centred on a field of the mean colour), resizes the padded
+ * field with one of two filters, and cuts crop x crop windows that need not tile the result (stride 308, a centre crop).
+ *
+ * The filters: SLIME_FILTER_BICUBIC is what slime_resample_ksize / slime_resample_coeffs produce (the _ex forms return exactly
+ * their tables for it); SLIME_FILTER_LANCZOS is Pillow's lanczos_filter -- support 3.0, sinc(x) * sinc(x / 3) on -3 <= x < 3, with
+ * sinc(0) = 1 and sin(pi x) / (pi x) otherwise -- through the same precompute_coeffs + normalize_coeffs_8bpc pipeline (double
+ * precision, no contraction, 22-bit fixed point), so the tables reproduce Image.resize(..., Image.LANCZOS) bit for bit. */
+enum { SLIME_FILTER_BICUBIC = 0, SLIME_FILTER_LANCZOS = 1 };
+int slime_resample_ksize_ex(int in_size, int out_size, int filter);
+int slime_resample_coeffs_ex(int in_size, int out_size, int filter, int* bounds_host, int* kk_host);
+
+/* A view job.  The result is bit-identical to: materialise the field (field_h x field_w pixels of colour bg with the box pasted at
+ * (paste_x, paste_y)) as a uint8 image, Image.resize((out_w, out_h), filter), crop the windows, rescale + normalise as
+ * slime_tile_normalize does, round to out_dtype.  The padding takes part in the resampling: taps near the box edge blend bg into
+ * the picture.  Launch 1 is the horizontal pass of the jobs that run both passes, over the columns their windows cover, into tmp;
+ * launch 2 is the vertical pass fused with windowing and normalisation (it reads the source when the widths agree, evaluates the
+ * horizontal taps itself when only the heights agree, copies when both agree).  Loads stay inside the job's image allocation
+ * ([img, img + (img_h - 1) * img_stride + img_w * 3)); only bytes of the box reach the result.
+ *   windows: crop x crop at (win_x0 + i * win_step, win_y0 + j * win_step) of the resized image, i < win_nx, j < win_ny, row-major
+ *            with j outer -> crops [first_crop, first_crop + win_nx * win_ny) of out; windows may overlap, each lies inside the
+ *            resized image.
+ *   out: out_dtype (F32 / BF16 / F16) [out_crops, 3, crop, crop]; crops no job owns are left untouched.
+ * Conventions of slime_slice_jobs: slime_view_jobs_plan (host only) fills the last three fields and returns the size of tmp; the
+ * table is passed twice (host copy: validated; device copy: read by the kernels); no upload, no allocation, capturable, at most two
+ * launches, every check before the first.  SLIME_EINVAL, with the limit named: n_jobs outside 1 .. SLIME_VIEW_MAX_JOBS, an empty
+ * image / box / field / output, a box that leaves its image, a paste that leaves its field, a window that leaves the resized image,
+ * win_nx / win_ny / win_step <= 0, an unknown filter, a pass whose sizes differ without tables or with ksize !=
+ * slime_resample_ksize_ex, crop ranges that overlap or leave [0, out_crops), a stride smaller than a row, out_dtype, plan fields
+ * that are not what slime_view_jobs_plan sets, more than 2^31 - 1 workgroups in a launch; SLIME_EWORKSPACE for a short or
+ * misaligned tmp (16 bytes). */
+typedef struct {
+    const uint8_t* img; long img_stride; int img_h, img_w;     /* DEVICE, packed RGB rows, stride in bytes: what loads may touch   */
+    int box_x0, box_y0, box_w, box_h;                          /* the part of the image that is used                               */
+    int field_w, field_h, paste_x, paste_y;                    /* the padded source; field == box and paste (0, 0): no padding     */
+    uint8_t bg[3];                                             /* colour of the field outside the box                              */
+    int out_w, out_h, filter;                                  /* == Image.resize((out_w, out_h), filter) of the field             */
+    const int* bounds_h; const int* kk_h; int ksize_h;         /* DEVICE tables field_w -> out_w; NULL / 0 if equal                */
+    const int* bounds_v; const int* kk_v; int ksize_v;         /* DEVICE tables field_h -> out_h; NULL / 0 if equal                */
+    int win_x0, win_y0, win_step, win_nx, win_ny;              /* the windows of the resized image                                 */
+    long first_crop;                                           /* windows -> crops [first_crop, + win_nx * win_ny) of out          */
+    long tmp_offset; int h_block0, v_block0;                   /* filled by slime_view_jobs_plan: byte offset of the [field_h, out_w, 3]
+                                                                * intermediate (both passes only, 16-byte aligned), first workgroup of
+                                                                * the job in launch 1 / launch 2                                       */
+} slime_view_job;
+#define SLIME_VIEW_MAX_JOBS 128
+int slime_view_jobs_plan(slime_view_job* jobs_host, int n_jobs, int crop, size_t* tmp_bytes_host);
+int slime_view_jobs(const slime_view_job* jobs_host, const slime_view_job* jobs_dev, int n_jobs, int crop,
+                    const float* mean3_host, const float* std3_host, void* out, long out_crops, int out_dtype,
+                    uint8_t* tmp, size_t tmp_bytes, void* stream);
+
 /* Text-guided router, scores (TextGuidedRouterCosine.forward, resampler/builder.py:186-201):
  * scores[t] = sum_l mask[l] * cos(img[t], text[l]) (mean over l if mask is NULL); img fp32 [T,H], text fp32
  * [L,H], mask uint8 [L]; ws: L+H+4 floats of scratch. */

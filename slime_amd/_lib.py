@@ -91,6 +91,20 @@ class SliceJob(C.Structure):
 
 SLICE_MAX_JOBS = 128
 
+
+class ViewJob(C.Structure):
+    _fields_ = [("img", c_void_p), ("img_stride", c_long), ("img_h", c_int), ("img_w", c_int),
+                ("box_x0", c_int), ("box_y0", c_int), ("box_w", c_int), ("box_h", c_int),
+                ("field_w", c_int), ("field_h", c_int), ("paste_x", c_int), ("paste_y", c_int), ("bg", C.c_ubyte * 3),
+                ("out_w", c_int), ("out_h", c_int), ("filter", c_int),
+                ("bounds_h", c_void_p), ("kk_h", c_void_p), ("ksize_h", c_int), ("bounds_v", c_void_p), ("kk_v", c_void_p), ("ksize_v", c_int),
+                ("win_x0", c_int), ("win_y0", c_int), ("win_step", c_int), ("win_nx", c_int), ("win_ny", c_int), ("first_crop", c_long),
+                ("tmp_offset", c_long), ("h_block0", c_int), ("v_block0", c_int)]
+
+
+VIEW_MAX_JOBS = 128
+FILTER_BICUBIC, FILTER_LANCZOS = 0, 1
+
 _P = C.POINTER
 _SIGNATURES = {
     "slime_abi_version": (c_int, []),
@@ -132,6 +146,11 @@ _SIGNATURES = {
     "slime_slice_jobs_plan": (c_int, [_P(SliceJob), c_int, c_int, _P(c_size_t)]),
     "slime_slice_jobs": (c_int, [_P(SliceJob), c_void_p, c_int, c_int, _P(c_float), _P(c_float), c_void_p, c_long, c_int, c_void_p,
                                  c_size_t, c_void_p]),
+    "slime_resample_ksize_ex": (c_int, [c_int, c_int, c_int]),
+    "slime_resample_coeffs_ex": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p]),
+    "slime_view_jobs_plan": (c_int, [_P(ViewJob), c_int, c_int, _P(c_size_t)]),
+    "slime_view_jobs": (c_int, [_P(ViewJob), c_void_p, c_int, c_int, _P(c_float), _P(c_float), c_void_p, c_long, c_int, c_void_p,
+                                c_size_t, c_void_p]),
     "slime_router_scores": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "slime_router_select": (c_int, [c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "slime_router_batched_workspace_floats": (c_size_t, [c_int, c_int, c_int]),

@@ -3,7 +3,8 @@
 Same function names, arguments and behaviour as the reference (llava/mm_utils.py:14-259) so drivers
 can switch imports; written from the algorithm, not from the text.  This is host code (PIL): in
 the reference it runs inside forked DataLoader workers, where HIP is unavailable.  The on-device
-counterpart (``process_anyres_image_gpu``) runs resize + pad + tile + normalise in HIP, bit-identically.
+counterpart (``process_anyres_image_gpu``) runs resize + pad + tile + normalise in HIP, bit-identically;
+``process_images_device`` does so for every ``image_aspect_ratio`` mode.
 """
 from __future__ import annotations
 
@@ -15,7 +16,8 @@ import numpy as np
 import torch
 from PIL import Image
 
-from .process_image import process_image_naive, process_image_any_res, expand2square  # noqa: F401 (API surface)
+from .constants import IMAGE_HEIGHT, IMAGE_WIDTH
+from .process_image import process_image_naive, process_image_any_res, expand2square, cal_num_of_slices  # noqa: F401 (API surface)
 
 CROP = 336   # the reference hard-codes (336, 336) in get_anyres_image_grid_shape (mm_utils.py:173)
 
@@ -200,7 +202,7 @@ def process_images_gpu_ragged(images, image_processor, model_cfg, device, dtype=
 def process_images_gpu(images, image_processor, model_cfg, device, dtype=torch.float32):
     """Device counterpart of :func:`process_images` for the SliME mode (``image_aspect_ratio='anyres'``):
     images (PIL or uint8 [H, W, 3] tensors, host or device) -> the same stacked tensor / list, resident on
-    ``device``.  Other modes raise: they are API-completeness modes of the reference served by the host path."""
+    ``device``.  Other modes raise here: :func:`process_images_device` serves them (and this one) on the device."""
     mode = getattr(model_cfg, "image_aspect_ratio", None)
     if mode != "anyres":
         raise NotImplementedError(f"process_images_gpu implements image_aspect_ratio='anyres' only (got {mode!r}); "
@@ -243,6 +245,92 @@ def process_images_gpu(images, image_processor, model_cfg, device, dtype=torch.f
     if all(x.shape == out[0].shape for x in out):
         return torch.stack(out, dim=0)
     return out
+
+
+def _squared(box, bg):
+    """(box, field, paste, bg) of :func:`expand2square` applied to the ``box`` = (x0, y0, w, h) of an image: centred on a square of
+    the longer side; a square box is its own field."""
+    _, _, w, h = box
+    side = max(w, h)
+    paste = (0, (w - h) // 2) if w > h else ((h - w) // 2, 0)
+    return box, (side, side), paste, tuple(int(v) for v in bg)
+
+
+def view_jobs_for(mode, size: Tuple[int, int], crop: int, bg) -> list:
+    """The view jobs (``ops.ViewSpec``) of ONE image of ``size`` = (width, height) under ``image_aspect_ratio = mode``, for a processor
+    whose ``shortest_edge`` and crop are both ``crop``: what :func:`process_images` does to it on the host, as integers.  The crops
+    of the jobs, in order, are the image's views.
+      'pad'             1 job: the image squared with ``bg``, bicubic to crop x crop.
+      'any_res'         1 + n jobs: the image and every box of ``slice_image_any_res``, each squared with ``bg``, bicubic to crop x crop.
+      'pad_then_devide' 2 jobs: the 'pad' view; the squared image, LANCZOS to 1024 x int(S * (1024 / S)) (1023 for some S, as in the
+                        reference's expression), cut into 336 x 336 windows at stride 308.
+      anything else     1 job (the bare processor): bicubic resize of the shortest edge to ``crop``, one centre window."""
+    from .ops import ViewSpec
+    from ._lib import FILTER_BICUBIC, FILTER_LANCZOS
+    W, H = int(size[0]), int(size[1])
+    if W <= 0 or H <= 0:
+        raise ValueError(f"view_jobs_for: empty image {W}x{H}")
+    one = (0, 0, crop, 1, 1)
+
+    def thumb(box):
+        return ViewSpec(*_squared(box, bg), (crop, crop), FILTER_BICUBIC, one)
+
+    whole = (0, 0, W, H)
+    if mode == "pad":
+        return [thumb(whole)]
+    if mode == "any_res":
+        bw, bh = cal_num_of_slices(W, H)
+        boxes = [(i * W // bw, j * H // bh, (i + 1) * W // bw - i * W // bw, (j + 1) * H // bh - j * H // bh)
+                 for j in range(bh) for i in range(bw)]
+        return [thumb(b) for b in [whole] + boxes]
+    if mode == "pad_then_devide":
+        if crop != IMAGE_WIDTH or crop != IMAGE_HEIGHT:
+            raise ValueError(f"view_jobs_for: 'pad_then_devide' cuts {IMAGE_WIDTH}x{IMAGE_HEIGHT} windows, the processor's crop is {crop}")
+        side = max(W, H)
+        ow, oh = 1024, int(float(side) * float(1024 / float(side)))                 # resize_image's expression, not 1024
+        nx, ny = len(range(0, ow - IMAGE_WIDTH + 1, 308)), len(range(0, oh - IMAGE_HEIGHT + 1, 308))
+        return [thumb(whole), ViewSpec(*_squared(whole, bg), (ow, oh), FILTER_LANCZOS, (0, 0, 308, nx, ny))]
+    short, long = (W, H) if W <= H else (H, W)
+    new_long = int(crop * long / short)                                             # ClipImageProcessor._resize_center_crop
+    nw, nh = (crop, new_long) if W <= H else (new_long, crop)
+    return [ViewSpec(whole, (W, H), (0, 0), tuple(int(v) for v in bg), (nw, nh), FILTER_BICUBIC,
+                     ((nw - crop) // 2, (nh - crop) // 2, crop, 1, 1))]
+
+
+def process_images_device(images, image_processor, model_cfg, device, dtype=torch.float32):
+    """:func:`process_images` on the device for EVERY ``image_aspect_ratio``: images (PIL or uint8 [H, W, 3] tensors, host or device)
+    -> the same stacked tensor / list (views of one flat crop buffer), resident on ``device``, bit-identical in fp32 and the rounded
+    fp32 result in bf16 / fp16.  'anyres' is :func:`process_images_gpu`; the other modes are view jobs (``ops.view_jobs``: only the
+    uint8 pixels cross PCIe, two launches and one table upload per 128 views, padding applied before the resampling as the host
+    does).  Needs ``size['shortest_edge'] == crop_size['height'] == crop_size['width']`` (the host path serves other processors).
+    Must be called from the main process (HIP is unusable in forked DataLoader workers)."""
+    from . import ops
+    mode = getattr(model_cfg, "image_aspect_ratio", None)
+    if mode == "anyres":
+        return process_images_gpu(images, image_processor, model_cfg, device, dtype)
+    crop, s = image_processor.crop_size["height"], image_processor.size["shortest_edge"]
+    if not (s == crop == image_processor.crop_size["width"]):
+        raise ValueError(f"process_images_device needs shortest_edge == crop height == crop width, got shortest_edge {s} and "
+                         f"crop_size {image_processor.crop_size['height']}x{image_processor.crop_size['width']}; use process_images")
+    if len(images) == 0:
+        raise ValueError("process_images_device: no images")
+    bg = tuple(int(x * 255) for x in image_processor.image_mean)
+    arrs = [torch.from_numpy(np.array(im.convert("RGB"))) if isinstance(im, Image.Image) else im for im in images]
+    arrs = [a.to(device, non_blocking=True) for a in arrs]
+    jobs, split, first = [], [], 0
+    for a in arrs:
+        specs = view_jobs_for(mode, (int(a.shape[1]), int(a.shape[0])), crop, bg)
+        for spec in specs:
+            jobs.append((a, spec, first))
+            first += spec.crops
+        split.append(sum(spec.crops for spec in specs))
+    flat = torch.empty((first, 3, crop, crop), dtype=dtype, device=device)
+    ops.view_jobs(jobs, crop, image_processor.image_mean, image_processor.image_std, flat)
+    if mode not in ("pad_then_devide", "any_res"):
+        return flat                                                                 # one view per image: [B, 3, crop, crop]
+    if all(n == split[0] for n in split):
+        return flat.view(len(split), split[0], 3, crop, crop)
+    return list(flat.split(split, dim=0))
 
 
 def process_images(images: Sequence[Image.Image], image_processor, model_cfg) -> Union[torch.Tensor, List[torch.Tensor]]:

@@ -793,25 +793,28 @@ def tile_normalize(canvas_u8: torch.Tensor, crop: int, mean, std, out_dtype: tor
     return out
 
 
-def resample_tables(in_size: int, out_size: int):
-    """Host-side Pillow coefficient tables (int32 numpy arrays): bounds [out, 2], kk [out, ksize]."""
+def resample_tables(in_size: int, out_size: int, filter: int = _lib.FILTER_BICUBIC):
+    """Host-side Pillow coefficient tables (int32 numpy arrays): bounds [out, 2], kk [out, ksize].  ``filter``: ``_lib.FILTER_BICUBIC``
+    (``Image.BICUBIC``) or ``_lib.FILTER_LANCZOS`` (``Image.LANCZOS``)."""
     import numpy as np
     lib = _lib.load()
-    ks = lib.slime_resample_ksize(in_size, out_size)
+    ks = lib.slime_resample_ksize_ex(in_size, out_size, filter)
+    if ks <= 0:
+        raise ValueError(f"resample_tables: bad sizes {in_size} -> {out_size} or filter {filter}")
     bounds = np.empty((out_size, 2), dtype=np.int32)
     kk = np.empty((out_size, ks), dtype=np.int32)
-    _lib.check(lib.slime_resample_coeffs(in_size, out_size, bounds.ctypes.data, kk.ctypes.data), "slime_resample_coeffs")
+    _lib.check(lib.slime_resample_coeffs_ex(in_size, out_size, filter, bounds.ctypes.data, kk.ctypes.data), "slime_resample_coeffs_ex")
     return bounds, kk
 
 
 _TABLE_CACHE = {}
 
 
-def _device_tables(in_size: int, out_size: int, device: torch.device):
-    key = (in_size, out_size, str(device))
+def _device_tables(in_size: int, out_size: int, device: torch.device, filter: int = _lib.FILTER_BICUBIC):
+    key = (in_size, out_size, str(device), filter)
     hit = _TABLE_CACHE.get(key)
     if hit is None:
-        b, k = resample_tables(in_size, out_size)
+        b, k = resample_tables(in_size, out_size, filter)
         hit = (torch.from_numpy(b).to(device), torch.from_numpy(k).to(device), k.shape[1])
         if len(_TABLE_CACHE) > 256:
             _TABLE_CACHE.clear()
@@ -931,6 +934,76 @@ def slice_jobs(jobs, crop: int, mean, std, out: torch.Tensor) -> None:
     s = (C.c_float * 3)(*[float(v) for v in std])
     _lib.check(lib.slime_slice_jobs(table, table_dev.data_ptr(), n, crop, m, s, out.data_ptr(), out.shape[0], dtype_code(out.dtype),
                                     _ptr(tmp), tmp_bytes.value, _stream()), "slime_slice_jobs")
+
+
+class ViewSpec(NamedTuple):
+    """One view job of :func:`view_jobs` (``slime_view_job`` without its pointers): the box ``(x0, y0, w, h)`` of the image that is
+    used, the field it is pasted into at ``paste`` = (x, y) over colour ``bg``, the resize of that field to ``out`` = (w, h) with
+    ``filter``, and the windows ``(x0, y0, step, nx, ny)`` of the resized image."""
+    box: tuple
+    field: tuple
+    paste: tuple
+    bg: tuple
+    out: tuple
+    filter: int
+    windows: tuple
+
+    @property
+    def crops(self) -> int:
+        return self.windows[3] * self.windows[4]
+
+
+def view_jobs(jobs, crop: int, mean, std, out: torch.Tensor) -> None:
+    """The slicer of the 'pad', 'pad_then_devide', 'any_res' and bare-processor modes (``slime_view_jobs``): per 128 jobs two launches
+    and one table upload.  ``jobs``: tuples ``(img, spec, first_crop)`` -- ``img`` a uint8 [H, W, 3] device image, ``spec`` a
+    :class:`ViewSpec`; the job's windows become the normalised crops ``out[first_crop : first_crop + spec.crops]``, bit-identical to
+    materialising the padded field, ``PIL.Image.resize(spec.out, filter)``, cropping and ``ClipImageProcessor.normalize_u8``.
+    ``out``: contiguous [crops, 3, crop, crop] device tensor (fp32 / bf16 / fp16); crops no job names keep their contents."""
+    lib = _lib.load()
+    _require_cuda(out, "out")
+    if out.dim() != 4 or tuple(out.shape[1:]) != (3, crop, crop) or not out.is_contiguous():
+        raise ValueError(f"view_jobs: out must be a contiguous [crops, 3, {crop}, {crop}] tensor, got {tuple(out.shape)}")
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s = (C.c_float * 3)(*[float(v) for v in std])
+    contiguous = {}                                        # one packed copy per image, however many jobs name it
+    for i0 in range(0, max(len(jobs), 1), _lib.VIEW_MAX_JOBS):
+        chunk = jobs[i0:i0 + _lib.VIEW_MAX_JOBS]
+        n = len(chunk)
+        table = (_lib.ViewJob * max(n, 1))()
+        keep = []                                          # tensors the table points to
+        for J, (img, spec, first_crop) in zip(table, chunk):
+            _require_cuda(img, "image")
+            if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+                raise ValueError(f"view_jobs expects uint8 [H, W, 3] images, got {img.dtype} {tuple(img.shape)}")
+            if img.stride(2) != 1 or img.stride(1) != 3:
+                if id(img) not in contiguous:
+                    contiguous[id(img)] = img.contiguous()
+                img = contiguous[id(img)]
+            keep.append(img)
+            J.img, J.img_stride, J.img_h, J.img_w = img.data_ptr(), img.stride(0), img.shape[0], img.shape[1]
+            J.box_x0, J.box_y0, J.box_w, J.box_h = spec.box
+            (J.field_w, J.field_h), (J.paste_x, J.paste_y) = spec.field, spec.paste
+            J.bg[0], J.bg[1], J.bg[2] = spec.bg
+            (J.out_w, J.out_h), J.filter = spec.out, spec.filter
+            J.win_x0, J.win_y0, J.win_step, J.win_nx, J.win_ny = spec.windows
+            J.first_crop = first_crop
+            if J.field_w != J.out_w:
+                b, k, J.ksize_h = _device_tables(J.field_w, J.out_w, img.device, spec.filter)
+                J.bounds_h, J.kk_h = b.data_ptr(), k.data_ptr()
+                keep += [b, k]
+            if J.field_h != J.out_h:
+                b, k, J.ksize_v = _device_tables(J.field_h, J.out_h, img.device, spec.filter)
+                J.bounds_v, J.kk_v = b.data_ptr(), k.data_ptr()
+                keep += [b, k]
+        tmp_bytes = C.c_size_t(0)
+        _lib.check(lib.slime_view_jobs_plan(table, n, crop, C.byref(tmp_bytes)), "slime_view_jobs_plan")
+        nbytes = n * C.sizeof(_lib.ViewJob)
+        staging = torch.empty((nbytes,), dtype=torch.uint8, pin_memory=True)
+        C.memmove(staging.data_ptr(), table, nbytes)
+        table_dev = staging.to(out.device, non_blocking=True)              # the one upload
+        tmp = torch.empty((tmp_bytes.value,), dtype=torch.uint8, device=out.device) if tmp_bytes.value else None
+        _lib.check(lib.slime_view_jobs(table, table_dev.data_ptr(), n, crop, m, s, out.data_ptr(), out.shape[0], dtype_code(out.dtype),
+                                       _ptr(tmp), tmp_bytes.value, _stream()), "slime_view_jobs")
 
 
 def router_scores(local_f: torch.Tensor, text: torch.Tensor, mask: Optional[torch.Tensor]) -> torch.Tensor:
