@@ -385,6 +385,59 @@ int slime_router_scores_batched(const float* img, const long long* row_off, cons
 int slime_router_select_batched(const float* scores, const int* n_rows, int B, int T_max, float temp, float topp,
                                 int* keep_idx, int* keep_count, void* stream);
 
+/* ---- the ATTENTION text-guided router (mm_resampler_type = 'qformer': TextGuidedRouterAttention.forward, resampler/builder.py:
+ * 149-162, eval path).  Per image, x [T, H] its local tokens and the VALID rows of its text (mask != 0; key_padding_mask = ~mask):
+ *     xq = ln_q(x); tk = ln_kv(text);  q = xq Wq^T + bq;  k | v = tk [Wk; Wv]^T + [bk; bv]       (cross_attn.in_proj_weight rows [q; k; v])
+ *     ctx = softmax(q k^T / sqrt(128)) v per head (heads = H / 128);  y = ln_post(ctx Wo^T + bo)
+ *     logit = relu(y W1^T + b1) . w2 + b2  (prob_proj);  scores = softmax(logit / temp) over the T tokens
+ * -- the array slime_router_select[_batched] takes (which applies the sampler's second softmax / temp and the top-p cut).  LayerNorm
+ * eps is nn.LayerNorm's 1e-5.  The matrix work runs through slime_gemm_ex / slime_attention (T operands, fp32 accumulation, one
+ * attention launch per image with n_kv = its valid keys: the masked keys are never gathered, so no mask reaches a kernel); the row
+ * passes between them are the two primitives below. */
+
+/* Gathered LayerNorm of any width: out_t[r] = T(LN(src[idx[r]])), r < rows; src fp32 [src_rows, D] (row stride D), idx DEVICE int64
+ * [rows] or NULL (identity), out_t compact T [rows, D].  D % 128 == 0, 128 <= D <= 8192 (4096, 5120 and the tiny models).  Two-pass
+ * variance with the row in registers, fp32 statistics, correctly rounded divisions by D; sums of depth 4 * ceil(D / 256) + 6.  An index
+ * outside [0, src_rows) reads nothing (its row is LN of zeros).  Pointers 16-byte aligned (idx 8). */
+int slime_ln_gather(const float* src, long src_rows, const long long* idx, int rows, int D, const float* w, const float* b,
+                    float eps, void* out_t, int dtype, void* stream);
+
+/* Probability head and per-image softmax: logit[r] = b2 + sum_j max(h[r, j], 0) * w2[j] over fp32 rows h [rows, N1] (N1 % 128 == 0;
+ * zero padding of w2 contributes exactly 0), logit fp32 [rows].  With scores != NULL: image b owns the next n_rows_host[b] logits
+ * (their sum must be rows) and scores[b * T_max + i] = softmax(logit / temp)[i], i < n_rows_host[b] (fp32, max-subtracted expf);
+ * entries past n_rows_host[b] are left untouched, an image with 0 rows gets no launch.  T_max <= 4096. */
+int slime_router_prob_head(const float* h, int rows, int N1, const float* w2, float b2, const int* n_rows_host, int B, int T_max,
+                           float temp, float* logit, float* scores, void* stream);
+
+typedef struct {
+    int H, heads, N1, dtype;                /* heads = H / 128; N1 = H / 4 rounded up to a multiple of 128; SLIME_BF16 / SLIME_F16 */
+    float eps;
+    const float* ln_q_w; const float* ln_q_b; const float* ln_kv_w; const float* ln_kv_b; const float* ln_post_w; const float* ln_post_b;
+    const void*  w_q;  const float* b_q;    /* T [H, H], f32 [H]: in_proj rows [0, H) x head_dim^-0.5 * log2(e) (SLIME_ATTN_Q_PRESCALE) */
+    const void*  w_kv; const float* b_kv;   /* T [2H, H], f32 [2H]: in_proj rows [H, 3H): k rows then v rows (ONE GEMM; row stride 2H)  */
+    const void*  w_o;  const float* b_o;    /* T [H, H], f32 [H]: cross_attn.out_proj                                                   */
+    const void*  w_1;  const float* b_1;    /* T [N1, H], f32 [N1]: prob_proj[0], rows past H / 4 zero                                  */
+    const float* w_2;  float b_2;           /* f32 [N1] (zero past H / 4), scalar: prob_proj[2]                                         */
+    const void* w_q_frag; const void* w_kv_frag; const void* w_o_frag; const void* w_1_frag;   /* optional slime_gemm_pack_b copies (then the
+                                                                                                 * row-major tensor may be NULL), or NULL */
+} slime_router_attn_desc;
+
+/* Scores for the B images of a step.  tokens fp32 [token_rows, H] (the fused adapters' token buffer); tok_idx DEVICE int64
+ * [sum_b n_rows_host[b]]: the token rows of image 0, then image 1, ...; text fp32 [text_rows, H] (the [B, L, H] text embeddings,
+ * flat); key_idx DEVICE int64: the text rows of the valid keys of every image THAT HAS TOKENS, image after image, n_keys_host[b]
+ * each (any pattern: left padding puts the zero rows in front); n_rows_host / n_keys_host HOST int32 [B], read during the call only
+ * (the attention launches take them by value).  scores fp32 padded [B, T_max]: row b gets n_rows_host[b] entries, the rest is left
+ * untouched; an image without tokens gets no launch.  ws: slime_router_attn_workspace_bytes(d, sum_T, sum_L) bytes, 256-byte
+ * aligned.  No allocation, no upload, no synchronisation; every check runs before the first launch.  SLIME_EINVAL, limit named:
+ * H % 128 != 0 or H > 8192, heads != H / 128, N1 % 128 != 0, T_max outside 1..4096 (the select kernel's limit), n_rows[b] outside
+ * 0..T_max, an image with tokens and NO valid key (the reference's softmax over an empty key set is NaN), a missing weight,
+ * misaligned pointers; SLIME_EWORKSPACE for a short or misaligned ws. */
+size_t slime_router_attn_workspace_bytes(const slime_router_attn_desc* d, long sum_T, long sum_L);
+int slime_router_attn_scores(const slime_router_attn_desc* d, const float* tokens, long token_rows, const long long* tok_idx,
+                             const int* n_rows_host, const float* text, long text_rows, const long long* key_idx,
+                             const int* n_keys_host, int B, int T_max, float temp, float* scores, void* ws, size_t ws_bytes,
+                             void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * CLIP vision tower (CLIPVisionTower.forward + feature_select, clip_encoder.py:36-58)
  * ---------------------------------------------------------------------------------------------- */

@@ -63,6 +63,16 @@ class ResamplerDesc(C.Structure):
                 ("w_k_frag", c_void_p), ("w_v_frag", c_void_p), ("w_o_frag", c_void_p)]
 
 
+class RouterAttnDesc(C.Structure):
+    """slime_router_attn_desc: the packed attention router (mm_resampler_type='qformer')."""
+    _fields_ = [("H", c_int), ("heads", c_int), ("N1", c_int), ("dtype", c_int), ("eps", c_float),
+                ("ln_q_w", c_void_p), ("ln_q_b", c_void_p), ("ln_kv_w", c_void_p), ("ln_kv_b", c_void_p),
+                ("ln_post_w", c_void_p), ("ln_post_b", c_void_p),
+                ("w_q", c_void_p), ("b_q", c_void_p), ("w_kv", c_void_p), ("b_kv", c_void_p), ("w_o", c_void_p), ("b_o", c_void_p),
+                ("w_1", c_void_p), ("b_1", c_void_p), ("w_2", c_void_p), ("b_2", c_float),
+                ("w_q_frag", c_void_p), ("w_kv_frag", c_void_p), ("w_o_frag", c_void_p), ("w_1_frag", c_void_p)]
+
+
 class MlpDesc(C.Structure):
     _fields_ = [("in_dim", c_int), ("hidden", c_int), ("dtype", c_int),
                 ("w1", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("b2", c_void_p), ("w1_frag", c_void_p), ("w2_frag", c_void_p)]
@@ -157,6 +167,12 @@ _SIGNATURES = {
     "slime_router_scores_batched": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                             c_void_p, c_void_p]),
     "slime_router_select_batched": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "slime_ln_gather": (c_int, [c_void_p, c_long, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p]),
+    "slime_router_prob_head": (c_int, [c_void_p, c_int, c_int, c_void_p, c_float, _P(c_int), c_int, c_int, c_float, c_void_p, c_void_p,
+                                       c_void_p]),
+    "slime_router_attn_workspace_bytes": (c_size_t, [_P(RouterAttnDesc), c_long, c_long]),
+    "slime_router_attn_scores": (c_int, [_P(RouterAttnDesc), c_void_p, c_long, c_void_p, _P(c_int), c_void_p, c_long, c_void_p, _P(c_int),
+                                         c_int, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "slime_vit_workspace_bytes": (c_size_t, [_P(VitDesc), c_int]),
     "slime_vit_residual_epilogue": (c_int, []),
     "slime_vit_check": (c_int, [_P(VitDesc)]),

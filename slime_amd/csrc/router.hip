@@ -220,3 +220,6 @@ extern "C" int slime_router_select_batched(const float* scores, const int* n_row
     SLIME_CHECK_LAUNCH("router_select_batched");
     return SLIME_OK;
 }
+
+// the attention router (mm_resampler_type = 'qformer'): a second producer of the score array the selection above reads
+#include "router_attn.inc"

@@ -113,6 +113,14 @@ def _adapter_operand_dtype(model, images: torch.Tensor) -> dict:
     return {"operand_dtype": images.dtype} if isinstance(model.mm_projector, (GatedBlock, HipMlp, HipLinear, Resampler)) else {}
 
 
+def _router_operand_dtype(model, images: torch.Tensor) -> dict:
+    """``{"operand_dtype": T}`` for the attention router (mm_resampler_type='qformer') when the call's images are 16-bit, as
+    ``_adapter_operand_dtype`` does for the adapter; the cosine router computes in fp32 and takes no such argument."""
+    if getattr(model.sampler, "router_type", None) != "qformer" or images.dtype not in (torch.bfloat16, torch.float16):
+        return {}
+    return {"operand_dtype": images.dtype}
+
+
 def _require_inference(model) -> None:
     """The HIP path has no backward.  The reference's pretrain / finetune stages train mm_projector and sampler through
     this code (train.py:1100-1130); silently detaching them under @torch.no_grad would freeze the adapter without a
@@ -363,7 +371,7 @@ class SlimeMetaForCausalLM(ABC):
             q = model.sampler.grid_size ** 2
             off, n_rows = [r + P for r in row0], [nw * nh * q for nw, nh in grids]
         # router: all B images in one launch pair, one D2H for the B kept counts (the reference syncs per image)
-        st = model.sampler.select_batched_device(tokens, off, n_rows, text_emb, text_mask)
+        st = model.sampler.select_batched_device(tokens, off, n_rows, text_emb, text_mask, **_router_operand_dtype(model, images))
         return tokens, off, n_rows, P, st, st.counts
 
     # ------------------------------------------------------------------ the hot path
@@ -452,7 +460,8 @@ class SlimeMetaForCausalLM(ABC):
                 for m_ in merged_list:
                     offs.append(o)
                     o += m_.shape[0]
-                keeps = model.sampler.select_batched(cat, offs, [m_.shape[0] for m_ in merged_list], text_emb, text_mask)
+                keeps = model.sampler.select_batched(cat, offs, [m_.shape[0] for m_ in merged_list], text_emb, text_mask,
+                                                     **_router_operand_dtype(model, images))
             outs = []
             for i in range(B):
                 pieces = []

@@ -1094,6 +1094,175 @@ def router_topp_batched(tokens: torch.Tensor, row_off: Sequence[int], n_rows: Se
     return [st.keep[b, :st.counts[b]].long() for b in range(len(n_rows))]
 
 
+# ---- the attention router (mm_resampler_type='qformer': TextGuidedRouterAttention, resampler/builder.py:94-162) ----------------------
+
+ROUTER_MAX_T = 4096          # slime_router_select's limit (ROUTER_MAX_T in csrc/router.hip)
+ROUTER_ATTN_MAX_H = 8192
+ROUTER_ATTN_EPS = 1e-5       # nn.LayerNorm's default (the Resampler's partial(nn.LayerNorm, eps=1e-6) is NOT used by the router)
+
+
+@dataclass
+class PackedRouterAttention:
+    H: int
+    heads: int
+    N1: int
+    dtype: torch.dtype
+    tensors: Dict[str, Optional[torch.Tensor]]
+    desc: _lib.RouterAttnDesc
+    ws: Workspace = field(default_factory=Workspace)
+
+
+def router_attention_host_tensors(sd: Dict[str, torch.Tensor], H: int, dtype: torch.dtype) -> Dict[str, torch.Tensor]:
+    """The pack-time algebra of ``pack_router_attention`` on the host (fp32 in, CPU tensors out): ``cross_attn.in_proj_weight`` rows
+    [q; k; v] become ``w_q`` = T(Wq s), ``b_q`` = bq s with s = 128^-0.5 log2(e) (slime_attention takes q pre-scaled) and ONE
+    ``w_kv`` [2H, H] = [Wk; Wv] (the k|v projection is one GEMM; attention reads k and v with row stride 2H); ``prob_proj`` is zero
+    padded from H / 4 to N1 = the next multiple of 128 (zero weight rows, zero bias, zero w2: the padding adds exactly 0)."""
+    if H % 128 != 0 or H < 128 or H > ROUTER_ATTN_MAX_H:
+        raise ValueError(f"attention router: hidden_size={H} must be a multiple of 128 (heads of 128) in 128..{ROUTER_ATTN_MAX_H}")
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"attention router: operand dtype {dtype} is not a 16-bit MFMA type")
+    f = lambda k: sd[k].detach().float().cpu()
+    in_w, in_b = f("cross_attn.in_proj_weight"), f("cross_attn.in_proj_bias")
+    assert in_w.shape == (3 * H, H) and in_b.shape == (3 * H,), "cross_attn.in_proj_* must be [3H, H] / [3H]"
+    s = 128 ** -0.5 * LOG2E
+    n1, N1 = H // 4, (H // 4 + 127) // 128 * 128
+    w1 = torch.zeros((N1, H), dtype=torch.float32)
+    b1 = torch.zeros((N1,), dtype=torch.float32)
+    w2 = torch.zeros((N1,), dtype=torch.float32)
+    w1[:n1], b1[:n1], w2[:n1] = f("prob_proj.0.weight"), f("prob_proj.0.bias"), f("prob_proj.2.weight").view(-1)
+    T = {"w_q": (in_w[:H] * s).to(dtype), "b_q": in_b[:H] * s, "w_kv": in_w[H:].to(dtype), "b_kv": in_b[H:].clone(),
+         "w_o": f("cross_attn.out_proj.weight").to(dtype), "b_o": f("cross_attn.out_proj.bias"),
+         "w_1": w1.to(dtype), "b_1": b1, "w_2": w2, "b_2": f("prob_proj.2.bias").view(())}
+    for ln in ("ln_q", "ln_kv", "ln_post"):
+        T[ln + "_w"], T[ln + "_b"] = f(ln + ".weight"), f(ln + ".bias")
+    return {k: v.contiguous() for k, v in T.items()}
+
+
+def pack_router_attention(sd: Dict[str, torch.Tensor], H: int, dtype: torch.dtype, device) -> PackedRouterAttention:
+    """``TextGuidedRouterAttention`` state dict -> kernel layout (``router_attention_host_tensors`` on ``device``, the four
+    matrices also in MFMA-fragment order where ``pack_b_frag`` applies).  ``query`` and ``self_attn.*`` are not packed: they take
+    no part in the forward pass."""
+    host = router_attention_host_tensors(sd, H, dtype)
+    b2 = float(host.pop("b_2"))
+    T: Dict[str, Optional[torch.Tensor]] = {k: v.to(device) for k, v in host.items()}
+    pack_static(T, ("w_q", "w_kv", "w_o", "w_1"))
+    d = _lib.RouterAttnDesc()
+    d.H, d.heads, d.N1, d.dtype, d.eps, d.b_2 = H, H // 128, T["w_2"].shape[0], dtype_code(dtype), ROUTER_ATTN_EPS, b2
+    for k, v in T.items():
+        setattr(d, k, None if v is None else v.data_ptr())
+    return PackedRouterAttention(H, H // 128, int(T["w_2"].shape[0]), dtype, T, d)
+
+
+def _router_attention_plan(row_off: Sequence[int], n_rows: Sequence[int], L: int, mask_host):
+    """Host side of the attention router: (tok_idx, key_idx, n_keys) -- the token rows of every image and the text rows
+    (b * L + l) of the valid keys of every image that has tokens, image after image.  Raises ValueError for an image with tokens
+    and no valid key (the reference's softmax over an empty key set is NaN) and for more tokens than the select kernel sorts."""
+    import numpy as np
+    B = len(n_rows)
+    T_max = max((int(n) for n in n_rows), default=0)
+    if T_max > ROUTER_MAX_T:
+        raise ValueError(f"attention router: {T_max} local tokens in one image, the selection sorts at most {ROUTER_MAX_T}")
+    tok, keys, n_keys = [], [], []
+    for b in range(B):
+        n = int(n_rows[b])
+        valid = np.arange(L, dtype=np.int64) if mask_host is None else np.nonzero(mask_host[b])[0].astype(np.int64)
+        n_keys.append(int(valid.size))
+        if n == 0:
+            continue
+        if valid.size == 0:
+            raise ValueError(f"attention router: image {b} has {n} local tokens and no valid text key (attention mask all zero)")
+        tok.append(np.arange(int(row_off[b]), int(row_off[b]) + n, dtype=np.int64))
+        keys.append(b * L + valid)
+    cat = lambda xs: np.concatenate(xs) if xs else np.zeros((0,), dtype=np.int64)
+    return cat(tok), cat(keys), n_keys
+
+
+def router_attention_scores(pra: PackedRouterAttention, tokens: torch.Tensor, row_off: Sequence[int], n_rows: Sequence[int],
+                            text: torch.Tensor, mask: Optional[torch.Tensor], temp: float) -> torch.Tensor:
+    """Attention-router scores for the B images of a step: fp32 [B, T_max], row b = softmax(logit / temp) over its n_rows[b] local
+    tokens (the rest of the row is unspecified) -- what ``TextGuidedRouterAttention.forward`` returns.  ``tokens`` fp32 [rows, H];
+    image b owns rows ``row_off[b] .. row_off[b] + n_rows[b] - 1``; ``text`` [B, L, H]; ``mask`` [B, L] or None (every key valid).
+    The valid-key lists are built on the HOST from the mask: a mask that lives on the device costs one [B, L] D2H copy (the fused
+    path's ``_pure_text_planned`` hands its host mask's device copy; pass a CPU mask to avoid the copy).  No other sync."""
+    assert tokens.dim() == 2 and tokens.dtype == torch.float32 and tokens.is_contiguous()
+    B, H = len(n_rows), tokens.shape[1]
+    assert text.dim() == 3 and text.shape[0] == B and text.shape[2] == H == pra.H, "text is [B, L, H] of the router's width"
+    L = text.shape[1]
+    mask_host = None if mask is None else mask.detach().ne(0).cpu().numpy()
+    tok_idx, key_idx, n_keys = _router_attention_plan(row_off, n_rows, L, mask_host)
+    lib = _lib.load()
+    _require_cuda(tokens, "tokens")
+    dev = tokens.device
+    T_max = max(1, max((int(n) for n in n_rows), default=0))
+    scores = torch.empty((B, T_max), dtype=torch.float32, device=dev)
+    if tok_idx.size == 0:
+        return scores
+    txt = text.to(device=dev, dtype=torch.float32).contiguous()
+    idx = torch.cat([torch.from_numpy(tok_idx), torch.from_numpy(key_idx)]).to(dev, non_blocking=True)   # one upload
+    sum_T, sum_L = int(tok_idx.size), int(key_idx.size)
+    need = lib.slime_router_attn_workspace_bytes(C.byref(pra.desc), sum_T, sum_L)
+    ws = pra.ws.get(need, dev)
+    base = (ws.data_ptr() + 255) // 256 * 256
+    nr = (C.c_int * B)(*[int(n) for n in n_rows])
+    nk = (C.c_int * B)(*n_keys)
+    _lib.check(lib.slime_router_attn_scores(C.byref(pra.desc), tokens.data_ptr(), tokens.shape[0], idx.data_ptr(), nr, txt.data_ptr(),
+                                            B * L, idx.data_ptr() + 8 * sum_T, nk, B, T_max, float(temp), scores.data_ptr(), base,
+                                            ws.numel() - (base - ws.data_ptr()), _stream()), "slime_router_attn_scores")
+    return scores
+
+
+def router_attention_select_batched_device(pra: PackedRouterAttention, tokens: torch.Tensor, row_off: Sequence[int],
+                                           n_rows: Sequence[int], text: torch.Tensor, mask: Optional[torch.Tensor], topp: float,
+                                           temp: float, want_scores: bool = False):
+    """``router_select_batched_device`` with the attention router's scores: the same ``RouterState`` (kept indices on the device,
+    counts on the host), so ``splice_routed`` and the callers of the cosine form take it unchanged.  The step's host syncs: the read
+    of the B kept counts, and the [B, L] mask copy of ``router_attention_scores`` if the mask lives on the device."""
+    B = len(n_rows)
+    dev = tokens.device
+    T_max = max((int(n) for n in n_rows), default=0)
+    if B == 0 or T_max == 0:                                        # nothing to route: no launch, no sync
+        st = RouterState(torch.zeros((B, 1), dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev),
+                         torch.tensor([int(o) for o in row_off], dtype=torch.int64).to(dev),
+                         torch.zeros((B,), dtype=torch.int32, device=dev), [0] * B)
+        return (st, None) if want_scores else st
+    scores = router_attention_scores(pra, tokens, row_off, n_rows, text, mask, temp)
+    lib = _lib.load()
+    off = torch.tensor([int(o) for o in row_off], dtype=torch.int64).to(dev, non_blocking=True)
+    cnt_in = torch.tensor([int(n) for n in n_rows], dtype=torch.int32).to(dev, non_blocking=True)
+    keep = torch.empty((B, T_max), dtype=torch.int32, device=dev)
+    cnt = torch.empty((B,), dtype=torch.int32, device=dev)
+    _lib.check(lib.slime_router_select_batched(scores.data_ptr(), cnt_in.data_ptr(), B, T_max, float(temp), float(topp),
+                                               keep.data_ptr(), cnt.data_ptr(), _stream()), "slime_router_select_batched")
+    st = RouterState(keep, cnt, off, cnt_in, cnt.cpu().tolist())     # the step's host sync
+    return (st, scores) if want_scores else st
+
+
+def ln_gather(src: torch.Tensor, idx: Optional[torch.Tensor], w: torch.Tensor, b: torch.Tensor, eps: float, out: torch.Tensor) -> torch.Tensor:
+    """out[r] = T(LayerNorm(src[idx[r]])) (slime_ln_gather): src fp32 [rows_in, D], idx int64 [rows] or None (identity), out T
+    [rows, D] written in place."""
+    lib = _lib.load()
+    _require_cuda(src, "src")
+    assert src.dtype == torch.float32 and src.dim() == 2 and src.is_contiguous() and out.is_contiguous()
+    assert idx is None or (idx.dtype == torch.int64 and idx.numel() == out.shape[0])
+    _lib.check(lib.slime_ln_gather(src.data_ptr(), src.shape[0], _ptr(idx), out.shape[0], src.shape[1], _ptr(w), _ptr(b), float(eps),
+                                   out.data_ptr(), dtype_code(out.dtype), _stream()), "slime_ln_gather")
+    return out
+
+
+def router_prob_head(h: torch.Tensor, w2: torch.Tensor, b2: float, n_rows: Optional[Sequence[int]], temp: float, logit: torch.Tensor,
+                     scores: Optional[torch.Tensor]) -> None:
+    """logit[r] = b2 + relu(h[r]) . w2 and, with ``scores`` [B, T_max], the per-image softmax(logit / temp) (slime_router_prob_head),
+    both written in place."""
+    lib = _lib.load()
+    _require_cuda(h, "h")
+    assert h.dtype == torch.float32 and h.dim() == 2 and h.is_contiguous()
+    B = len(n_rows) if n_rows is not None else 0
+    nr = (C.c_int * max(B, 1))(*[int(n) for n in (n_rows or [0])])
+    _lib.check(lib.slime_router_prob_head(h.data_ptr(), h.shape[0], h.shape[1], _ptr(w2), float(b2), nr, B,
+                                          scores.shape[1] if scores is not None else 0, float(temp), logit.data_ptr(), _ptr(scores),
+                                          _stream()), "slime_router_prob_head")
+
+
 # ------------------------------------------------------------------------------------------------
 # after the visual tokens (SURVEY.md section 8 row f-2): splice + Llama prefill attention
 # ------------------------------------------------------------------------------------------------

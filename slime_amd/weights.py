@@ -191,6 +191,28 @@ def make_adapter_state_dict(cfg: AdapterConfig = ADAPTER_8B, seed: int = 4321) -
     return sd
 
 
+def make_router_attention_state_dict(H: int, seed: int = 2468) -> Dict[str, torch.Tensor]:
+    """fp32 state dict of ``TextGuidedRouterAttention`` (resampler/builder.py:120-136; key names and shapes of the reference's
+    ``selector``), seeded and NON-DEGENERATE: LayerNorm weights 1 + 0.1 n, matrices scaled by fan_in^-1/2 so that the logits vary
+    (with the reference's 0.02 initialisation every score is 1 / T to six digits and a comparison shows nothing).  ``query`` and
+    ``self_attn.*`` take no part in the forward pass; they are there so that a checkpoint loads under ``strict=True``."""
+    g = _gen(seed)
+    sd: Dict[str, torch.Tensor] = {"query": _normal(g, (1, H), 0.02)}
+    for attn in ("self_attn", "cross_attn"):
+        sd[f"{attn}.in_proj_weight"] = _normal(g, (3 * H, H), H ** -0.5)
+        sd[f"{attn}.in_proj_bias"] = _normal(g, (3 * H,), 0.02)
+        sd[f"{attn}.out_proj.weight"] = _normal(g, (H, H), H ** -0.5)
+        sd[f"{attn}.out_proj.bias"] = _normal(g, (H,), 0.02)
+    for ln in ("ln_q", "ln_kv", "ln_post"):
+        sd[ln + ".weight"] = _normal(g, (H,), 0.1, 1.0)
+        sd[ln + ".bias"] = _normal(g, (H,), 0.05)
+    sd["prob_proj.0.weight"] = _normal(g, (H // 4, H), H ** -0.5)
+    sd["prob_proj.0.bias"] = _normal(g, (H // 4,), 0.02)
+    sd["prob_proj.2.weight"] = _normal(g, (1, H // 4), (H // 4) ** -0.5)
+    sd["prob_proj.2.bias"] = _normal(g, (1,), 0.02)
+    return sd
+
+
 def sub_state(sd: Dict[str, torch.Tensor], prefix: str) -> Dict[str, torch.Tensor]:
     """Entries under ``prefix`` with the prefix removed."""
     n = len(prefix)
