@@ -633,6 +633,23 @@ int slime_splice_routed(const void* table, int table_dtype, long table_rows, lon
                         int mid_dtype, const int64_t* src, void* out, int out_dtype,
                         long rows, int H, void* stream);
 
+/* The same splice for the un-sampled LLaVA-NeXT merge (mm_patch_merge_type 'spatial' / 'spatial_unpad', llava_arch.py:293-333): the
+ * merged per-image features are never built; the host plan names every output row's source.
+ *   tokens: fp32 [token_rows, H], the projector's output over all crops of the batch (row crop * P + patch).
+ *   extra:  [extra_rows, H] of extra_dtype: rows appended behind the tokens (model.image_newline).
+ *   src: DEVICE int64 [rows].  src >= 0: table row; src == -1: zeros; src <= -2: k = -2 - src: k < token_rows token row k;
+ *        token_rows <= k < token_rows + extra_rows row k - token_rows of extra.
+ * Values: a text row as in slime_splice_rows (equal dtypes bit for bit, else a cast); a token row is
+ * out_dtype(mid_dtype(tokens[k, :])) (mid_dtype == SLIME_F32: no middle rounding); an extra row is copied bit for bit when
+ * extra_dtype == out_dtype, else cast once (no middle rounding).  The output row is zeroed and no source is read when k >=
+ * token_rows + extra_rows or a table id lies outside the table.  tokens may be NULL iff token_rows == 0, extra iff extra_rows == 0.
+ * SLIME_EINVAL, limit named: null src, out or table; rows or H <= 0; a negative row count; a dtype other than F32 / BF16 / F16;
+ * H * sizeof(out element) or H * 4 not a multiple of 16; out, table, tokens or extra not 16-byte aligned. */
+int slime_splice_merged(const void* table, int table_dtype, long table_rows,
+                        const float* tokens, long token_rows, int mid_dtype,
+                        const void* extra, int extra_dtype, long extra_rows,
+                        const int64_t* src, void* out, int out_dtype, long rows, int H, void* stream);
+
 /* Rotary position embedding, in place, on the first n_rot_heads heads (head_dim 128) of every row of a packed qkv buffer
  * (row stride in elements): HF apply_rotary_pos_emb / rotate_half as called at llama_flash_attn_monkey_patch.py:51-54,
  * angle = (float)pos[row] * inv_freq[i], i < 64 (inv_freq: DEVICE fp32 [64], computed by the host exactly as

@@ -203,6 +203,8 @@ _SIGNATURES = {
     "slime_splice_rows": (c_int, [c_void_p, c_int, c_long, c_void_p, c_int, c_long, c_void_p, c_void_p, c_int, c_long, c_int, c_void_p]),
     "slime_splice_routed": (c_int, [c_void_p, c_int, c_long, c_long, c_void_p, c_long, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                     c_void_p, c_int, c_void_p, c_void_p, c_int, c_long, c_int, c_void_p]),
+    "slime_splice_merged": (c_int, [c_void_p, c_int, c_long, c_void_p, c_long, c_int, c_void_p, c_int, c_long, c_void_p, c_void_p, c_int,
+                                    c_long, c_int, c_void_p]),
     "slime_rope": (c_int, [c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_float, c_int, c_void_p]),
     "slime_prefill_attention": (c_int, [c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_void_p, c_long,
                                         c_long, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),

@@ -8,6 +8,9 @@
 //   slime_splice_routed      the same rows without the per-image feature tensors in between: an image row names (image, position) and
 //                            is resolved on the device from the batched router's arrays and the fp32 token buffer (opt-in:
 //                            cfg.fused_splice), with the two roundings of the per-image path -- the same bits.
+//   slime_splice_merged      the same rows for the un-sampled LLaVA-NeXT merge ('spatial' / 'spatial_unpad'): an image row names a row
+//                            of the projector's fp32 output (or the image_newline row) directly, the merged per-image features are
+//                            never built; same two roundings, same bits.
 //   slime_rope               RoPE on the q and k heads of a packed qkv buffer, in place (HF rotate_half convention: pairs
 //                            (i, i + d/2); fp32 cos/sin of pos * inv_freq), q additionally scaled by head_dim^-0.5 * log2 e
 //                            (the attention kernels work in log2 units).
@@ -187,6 +190,90 @@ extern "C" int slime_splice_routed(const void* table, int table_dtype, long tabl
                        table_rows, sep_id, tokens, token_rows, local_row_off, n_rows, B, P, T_max, keep_idx, keep_count, mid_dtype,
                        reinterpret_cast<const long long*>(src), out, out_dtype, rows, H);
     SLIME_CHECK_LAUNCH("splice_routed");
+    return SLIME_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ merged splice
+// One wave per output row, as the two kernels above, for the un-sampled LLaVA-NeXT merge ('spatial' / 'spatial_unpad'): the merged
+// per-image features are never materialised, the host plan names every output row's source directly.
+//   src >= 0: table row (splice_rows' rule); src == -1: zeros; src <= -2: k = -2 - src: k < token_rows row k of the fp32 projector
+//   output through the two roundings fp32 -> mid -> out (16 B per lane in and out); token_rows <= k < token_rows + extra_rows row
+//   k - token_rows of `extra` (model.image_newline), one cast or a bit copy, no middle rounding.
+// A source that resolves outside its tensor is never dereferenced: the row is zeroed.
+__global__ void __launch_bounds__(256) splice_merged_kernel(const void* table, int table_dtype, long table_rows, const float* tokens,
+                                                            long token_rows, int mid_dtype, const void* extra, int extra_dtype,
+                                                            long extra_rows, const long long* src, void* out, int out_dtype, long rows,
+                                                            int H) {
+    const int lane = threadIdx.x & 63;
+    const long r = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (r >= rows) return;
+    const long long s = src[r];
+    const int es_out = out_dtype == SLIME_F32 ? 4 : 2;
+    char* o = reinterpret_cast<char*>(out) + (size_t)r * H * es_out;
+    long long krow = -1, crow = -1;                       // fp32 token row / row of a typed tensor (table or extra); both -1: zeros
+    const void* cbase = table;
+    int cdt = table_dtype;
+    if (s >= 0) {
+        if (s < table_rows) crow = s;
+    } else if (s <= -2) {
+        const long long k = -2 - s;                       // s >= INT64_MIN, so k <= INT64_MAX - 1: no overflow
+        if (k < token_rows) krow = k;
+        else if (k - token_rows < extra_rows) { crow = k - token_rows; cbase = extra; cdt = extra_dtype; }
+    }
+    if (krow < 0 && crow < 0) {
+        for (int c = lane * 16; c < H * es_out; c += 1024) *reinterpret_cast<u32x4*>(o + c) = u32x4{0u, 0u, 0u, 0u};
+        return;
+    }
+    if (krow >= 0) {                                      // image token: fp32 -> mid -> out
+        const float* t = tokens + (size_t)krow * H;
+        if (out_dtype == SLIME_F32) {
+            for (int c = lane * 4; c < H; c += 256) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(t + c);
+                *reinterpret_cast<f32x4*>(o + (size_t)c * 4) = f32x4{round_through(v[0], mid_dtype), round_through(v[1], mid_dtype),
+                                                                      round_through(v[2], mid_dtype), round_through(v[3], mid_dtype)};
+            }
+            return;
+        }
+        for (int c = lane * 8; c < H; c += 512) {         // a 16-bit output row of whole 16-byte pieces: H is a multiple of 8
+            const f32x4 v0 = *reinterpret_cast<const f32x4*>(t + c), v1 = *reinterpret_cast<const f32x4*>(t + c + 4);
+            u32x4 w;
+            w[0] = pack2_as(round_through(v0[0], mid_dtype), round_through(v0[1], mid_dtype), out_dtype);
+            w[1] = pack2_as(round_through(v0[2], mid_dtype), round_through(v0[3], mid_dtype), out_dtype);
+            w[2] = pack2_as(round_through(v1[0], mid_dtype), round_through(v1[1], mid_dtype), out_dtype);
+            w[3] = pack2_as(round_through(v1[2], mid_dtype), round_through(v1[3], mid_dtype), out_dtype);
+            *reinterpret_cast<u32x4*>(o + (size_t)c * 2) = w;
+        }
+        return;
+    }
+    if (cdt == out_dtype) {                               // text token / newline row of the output's type: bit copy
+        const char* p = reinterpret_cast<const char*>(cbase) + (size_t)crow * H * es_out;
+        for (int c = lane * 16; c < H * es_out; c += 1024) *reinterpret_cast<u32x4*>(o + c) = *reinterpret_cast<const u32x4*>(p + c);
+        return;
+    }
+    for (int c = lane; c < H; c += 64) store_from_float(out, out_dtype, (size_t)r * H + c, load_as_float(cbase, cdt, (size_t)crow * H + c));
+}
+
+extern "C" int slime_splice_merged(const void* table, int table_dtype, long table_rows, const float* tokens, long token_rows,
+                                   int mid_dtype, const void* extra, int extra_dtype, long extra_rows, const int64_t* src, void* out,
+                                   int out_dtype, long rows, int H, void* stream) {
+    SLIME_REQUIRE(src && out && table, "splice_merged: null src, out or table");
+    SLIME_REQUIRE(rows > 0 && H > 0, "splice_merged: rows=%ld H=%d must be positive", rows, H);
+    SLIME_REQUIRE(table_rows >= 0 && token_rows >= 0 && extra_rows >= 0,
+                  "splice_merged: table_rows=%ld token_rows=%ld extra_rows=%ld must not be negative", table_rows, token_rows, extra_rows);
+    SLIME_REQUIRE((tokens != nullptr) == (token_rows != 0), "splice_merged: tokens may be null exactly when token_rows=%ld is 0", token_rows);
+    SLIME_REQUIRE((extra != nullptr) == (extra_rows != 0), "splice_merged: extra may be null exactly when extra_rows=%ld is 0", extra_rows);
+    auto ok = [](int dt) { return dt == SLIME_F32 || dt == SLIME_BF16 || dt == SLIME_F16; };
+    SLIME_REQUIRE(ok(table_dtype) && ok(mid_dtype) && ok(out_dtype) && (!extra || ok(extra_dtype)),
+                  "splice_merged: bad dtype (table %d, mid %d, extra %d, out %d: F32, BF16 or F16)", table_dtype, mid_dtype, extra_dtype,
+                  out_dtype);
+    SLIME_REQUIRE((H * (out_dtype == SLIME_F32 ? 4 : 2)) % 16 == 0 && (H * 4) % 16 == 0,
+                  "splice_merged: fp32 token rows and output rows must be multiples of 16 bytes (H=%d)", H);
+    SLIME_REQUIRE(((uintptr_t)out % 16) == 0 && ((uintptr_t)table % 16) == 0 && ((uintptr_t)tokens % 16) == 0 && ((uintptr_t)extra % 16) == 0,
+                  "splice_merged: out, table, tokens and extra must be 16-byte aligned");
+    hipLaunchKernelGGL(splice_merged_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, table, table_dtype,
+                       table_rows, tokens, token_rows, mid_dtype, extra, extra_dtype, extra_rows, reinterpret_cast<const long long*>(src),
+                       out, out_dtype, rows, H);
+    SLIME_CHECK_LAUNCH("splice_merged");
     return SLIME_OK;
 }
 

@@ -25,6 +25,7 @@ tower hands over fp32 features: ``images_mask``, ``use_local_only`` / ``use_glob
 """
 from __future__ import annotations
 
+import functools
 from abc import ABC, abstractmethod
 from typing import Optional, Sequence
 
@@ -235,6 +236,115 @@ def routed_src(src, feat_lens):
     return out
 
 
+def unpad_window(original_size, cur_h: int, cur_w: int):
+    """``(r0, r1, c0, c1)``: the rows and columns of a ``cur_h x cur_w`` raster that the reference's ``unpad_image`` keeps for an image
+    of ``original_size = (width, height)`` (llava_arch.py:122-150) -- its arithmetic restated exactly: Python float division and
+    ``int()``, ``padding = (cur - new) // 2`` trimmed from both ends, so an odd remainder keeps one row or column more than ``new``."""
+    original_width, original_height = (int(v) for v in original_size)
+    cur_h, cur_w = int(cur_h), int(cur_w)
+    if original_width / original_height > cur_w / cur_h:
+        scale_factor = cur_w / original_width
+        new_height = int(original_height * scale_factor)
+        padding = (cur_h - new_height) // 2
+        r0, r1, _ = slice(padding, cur_h - padding).indices(cur_h)
+        return r0, max(r0, r1), 0, cur_w
+    scale_factor = cur_h / original_height
+    new_width = int(original_width * scale_factor)
+    padding = (cur_w - new_width) // 2
+    c0, c1, _ = slice(padding, cur_w - padding).indices(cur_w)
+    return 0, cur_h, c0, max(c0, c1)
+
+
+MERGE_ZERO, MERGE_NEWLINE = -1, -2          # entries of a merge plan that name no projector row
+
+
+@functools.lru_cache(maxsize=4096)
+def _grid_of(width: int, height: int, pinpoints: str, crop: int):
+    """``get_anyres_image_grid_shape`` per (size, pinpoints, crop): the merge plan runs on the host in front of the step's first launch,
+    where parsing the pinpoint string once per image is most of its time."""
+    nw, nh = get_anyres_image_grid_shape((width, height), pinpoints, crop)
+    return int(nw), int(nh)
+
+
+def unsampled_merge_plans(split_sizes, image_sizes, images_mask, cfg, tower, has_newline: bool):
+    """The LLaVA-NeXT merge of un-sampled crops (llava_arch.py:293-333) as integer host logic: per image an int64 array over its
+    feature positions, in the reference's order.  Entry ``k >= 0``: flat token row ``crop * P + patch`` of the batch's projector output
+    (all crops of all images, P rows each); ``MERGE_ZERO``: a zero row (the reference's ``zeros_like`` column behind every kept raster
+    row, :318-319); ``MERGE_NEWLINE``: ``model.image_newline`` (behind a single-crop image, :327-331).  Every refusal is raised here,
+    before any device work."""
+    import numpy as np
+    merge_type = getattr(cfg, "mm_patch_merge_type", "flat")
+    unpad = "unpad" in merge_type
+    side = int(tower.num_patches_per_side)
+    P = side * side
+    rows_per_crop = int(tower.num_patches) + (1 if getattr(tower, "select_feature", "patch") == "cls_patch" else 0)
+    if rows_per_crop != P:
+        raise ValueError(f"mm_patch_merge_type={merge_type!r} needs {side}x{side} = {P} tower rows per crop, the tower returns "
+                         f"{rows_per_crop} (mm_vision_select_feature='cls_patch' is not a raster)")
+    multi = any(s > 1 for s in split_sizes)
+    if multi and getattr(cfg, "image_aspect_ratio", "square") != "anyres":
+        raise NotImplementedError(f"mm_patch_merge_type={merge_type!r} merges several crops only for image_aspect_ratio='anyres', "
+                                  f"not {getattr(cfg, 'image_aspect_ratio', 'square')!r} (llava_arch.py:312)")
+    if multi and (image_sizes is None or len(image_sizes) != len(split_sizes)):
+        raise ValueError(f"mm_patch_merge_type={merge_type!r} needs one image size per image: {len(split_sizes)} images, "
+                         f"{'no' if image_sizes is None else len(image_sizes)} image_sizes")
+    if images_mask is not None and len(images_mask) != len(split_sizes):
+        raise ValueError(f"images_mask has {len(images_mask)} entries for {len(split_sizes)} images")
+    patch = np.arange(P, dtype=np.int64)
+    plans, crop0 = [], 0
+    for i, s in enumerate(split_sizes):
+        if s < 1:
+            raise ValueError(f"image {i} has no crops")
+        base = crop0 * P + patch
+        if s == 1:                                                          # :325-331
+            if unpad and not has_newline:
+                raise ValueError(f"mm_patch_merge_type={merge_type!r}: image {i} has one crop and takes model.image_newline, which "
+                                 "this model does not have (it is created when the config names 'unpad' at construction)")
+            plans.append(np.concatenate([base, [MERGE_NEWLINE]]).astype(np.int64) if unpad else base)
+            crop0 += s
+            continue
+        local = np.arange(crop0 + 1, crop0 + s, dtype=np.int64)
+        if images_mask is not None:                                         # :300-302
+            m = images_mask[i]
+            m = m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m)
+            sel = np.nonzero(m[1:])[0]
+            if sel.size and int(sel.max()) >= s - 1:
+                raise ValueError(f"image {i}: images_mask marks local crop {int(sel.max())} of {s - 1}")
+            local = local[sel]
+        w_i, h_i = (int(v) for v in image_sizes[i])
+        nw, nh = _grid_of(w_i, h_i, str(cfg.image_grid_pinpoints), int(tower.config.image_size))
+        if nw * nh != local.shape[0]:
+            raise ValueError(f"image {i}: grid {nw}x{nh} does not match {local.shape[0]} local crops")
+        # raster[y, x] of the nh*side x nw*side canvas: view(nh, nw, side, side).permute(0, 2, 1, 3)
+        raster = (local.reshape(nh, 1, nw, 1) * P + patch.reshape(1, side, 1, side)).reshape(nh * side, nw * side)
+        if unpad:                                                           # :314-320
+            r0, r1, c0, c1 = unpad_window(image_sizes[i], nh * side, nw * side)
+            raster = raster[r0:r1, c0:c1]
+            raster = np.concatenate([raster, np.full((raster.shape[0], 1), MERGE_ZERO, dtype=np.int64)], axis=1)
+        plans.append(np.concatenate([base, raster.reshape(-1)]))
+        crop0 += s
+    return plans
+
+
+def merged_src(src, plans, token_rows: int):
+    """``splice_plan``'s ``src`` (built with the plan lengths as ``feat_lens``) for ``ops.splice_merged``: every entry ``-2 - k`` is
+    looked up in the concatenated per-image merge plans: a projector row r becomes ``-2 - r``, a zero row -1, the newline row
+    ``-2 - token_rows`` (row 0 of ``extra``); token ids and -1 stay."""
+    import numpy as np
+    src = np.asarray(src, dtype=np.int64)
+    allp = np.concatenate([np.asarray(p, dtype=np.int64) for p in plans]) if len(plans) else np.zeros((0,), dtype=np.int64)
+    out = src.copy()
+    m = src <= -2
+    k = -2 - src[m]
+    if k.size and int(k.max()) >= allp.shape[0]:
+        raise ValueError("splice plan names a feature row past the last image")
+    v = allp[k]
+    if v.size and int(v.max()) >= token_rows:
+        raise ValueError(f"merge plan names projector row {int(v.max())} of {token_rows}")
+    out[m] = np.where(v >= 0, -2 - v, np.where(v == MERGE_ZERO, -1, -2 - np.int64(token_rows)))
+    return out
+
+
 def _pure_text_order(ids, padding_side: str = "right", max_len=None):
     """Column of ``ids`` [B, L] behind every row of get_pure_text_embedding's output, -1 for the zero rows that stand in for the
     <image> placeholders (appended; prepended for left padding), cut to ``max_len`` (llava_arch.py:162-210).  int64 [B, L']."""
@@ -272,6 +382,10 @@ class SlimeMetaModel:
             self.sampler = build_vision_sampler(config)
             t = getattr(config, "mm_resampler_type", None)
             self.has_sampler = t != "identity" and t is not None and t != "spatial"
+            if "unpad" in getattr(config, "mm_patch_merge_type", ""):
+                # the row 'spatial_unpad' appends to a single-crop image (llava_arch.py:41-44, :327-331); zeros where the reference
+                # leaves uninitialised memory: a checkpoint that carries the key overwrites it
+                self.image_newline = nn.Parameter(torch.zeros(config.hidden_size))
 
     def get_vision_tower(self):
         vt = getattr(self, "vision_tower", None)
@@ -474,15 +588,40 @@ class SlimeMetaForCausalLM(ABC):
                 outs.append(torch.cat(pieces, dim=0).to(out_dtype).unsqueeze(0))
             return outs, split_sizes
 
-        T16 = _adapter_operand_dtype(model, images)
         if split_sizes is not None:                                               # no sampler: per-image lists
-            feats = tower(images, out_dtype=torch.float32)
-            proj = model.mm_projector(feats, out_dtype=out_dtype, **T16) if not isinstance(model.mm_projector, GatedBlock) \
-                else torch.cat([model.mm_projector(f, out_dtype=out_dtype, **T16) for f in torch.split(feats, 1)], 0)
-            return list(torch.split(proj, split_sizes, dim=0)), split_sizes
+            return list(torch.split(self._project_crops(images, out_dtype), split_sizes, dim=0)), split_sizes
 
+        T16 = _adapter_operand_dtype(model, images)
         feats = tower(images, out_dtype=torch.float32)
         return model.mm_projector(feats, out_dtype=out_dtype, **T16), split_sizes
+
+    def _project_crops(self, images, out_dtype):
+        """Tower and ``mm_projector`` once over all crops of a batch without a sampler (llava_arch.py:257-260): [crops, P, H] of
+        ``out_dtype`` (an IdentityMap hands the tower's fp32 features through whatever is asked for)."""
+        model = self.get_model()
+        T16 = _adapter_operand_dtype(model, images)
+        feats = model.get_vision_tower()(images, out_dtype=torch.float32)
+        if not isinstance(model.mm_projector, GatedBlock):
+            return model.mm_projector(feats, out_dtype=out_dtype, **T16)
+        return torch.cat([model.mm_projector(f, out_dtype=out_dtype, **T16) for f in torch.split(feats, 1)], 0)
+
+    def _merged_unsampled(self, images, split_sizes, image_sizes, images_mask):
+        """The un-sampled 'spatial' / 'spatial_unpad' branch without its per-image tensors: the merge plans (host; every refusal is
+        raised before the device is touched), the projector's fp32 output over all crops as [crops * P, H], and the dtype the
+        features of ``encode_images`` carry for this model -- the middle rounding ``slime_splice_merged`` applies."""
+        from .multimodal_projector.builder import IdentityMap
+        model = self.get_model()
+        plans = unsampled_merge_plans(list(split_sizes), image_sizes, images_mask, self.config, model.get_vision_tower(),
+                                      getattr(model, "image_newline", None) is not None)
+        _require_inference(model)
+        with torch.no_grad():
+            tokens = self._project_crops(images, torch.float32)
+        P = model.get_vision_tower().num_patches
+        if tokens.dim() != 3 or tokens.shape[0] != sum(split_sizes) or tokens.shape[1] != P or tokens.dtype != torch.float32:
+            raise ValueError(f"mm_projector returned {tuple(tokens.shape)} {tokens.dtype} for {sum(split_sizes)} crops of {P} rows: the "
+                             "merged splice needs fp32 [crops, P, H]")
+        mid = torch.float32 if isinstance(model.mm_projector, IdentityMap) else images.dtype
+        return plans, tokens.reshape(-1, tokens.shape[-1]), mid
 
 
     # ------------------------------------------------------------------ splice (the step after the hot path)
@@ -491,7 +630,10 @@ class SlimeMetaForCausalLM(ABC):
         """Signature, branches and return tuple of llava_arch.py:274-459.  The visual features come from ``encode_images``
         above; the splice itself is an integer plan on the host (``splice_plan``: token ids are a few hundred ints) and ONE
         device launch (``slime_splice_rows``) that writes the whole padded [B, max_len, H] embedding tensor -- embedding
-        lookup, image rows, zero padding -- where the reference runs per-sequence embed / split / cat / stack."""
+        lookup, image rows, zero padding -- where the reference runs per-sequence embed / split / cat / stack.  Without a sampler,
+        'spatial' / 'spatial_unpad' (the LLaVA-NeXT crop merge, :293-333) is part of the same plan: ``unsampled_merge_plans`` names the
+        projector row, zero row or ``image_newline`` behind every feature position and ``slime_splice_merged`` moves the rows from the
+        projector's fp32 output in that one launch; no per-image feature tensor is built."""
         vision_tower = self.get_vision_tower()
         if vision_tower is None or images is None or input_ids.shape[1] == 1:
             return input_ids, position_ids, attention_mask, past_key_values, None, labels
@@ -505,7 +647,7 @@ class SlimeMetaForCausalLM(ABC):
         vocab = self.get_model().embed_tokens.weight.shape[0]
         if getattr(self.get_model(), "has_sampler", False) and ids_np.size:
             _check_token_ids(ids_np.reshape(-1), vocab)
-        routed = None
+        routed = merged = am_np = lab_np = None
         if type(images) is list or images.ndim == 5:
             if type(images) is list:
                 images = [x.unsqueeze(0) if x.ndim == 3 else x for x in images]
@@ -517,7 +659,13 @@ class SlimeMetaForCausalLM(ABC):
                 with torch.no_grad():
                     routed = self._fused_route(concat_images, input_ids, split_sizes, attention_mask, images_mask, image_sizes, labels, True)
             feats = []
-            if routed is None:
+            if not getattr(self.get_model(), "has_sampler", False) and merge_type.startswith("spatial"):
+                # LLaVA-NeXT merge of un-sampled crops (:293-333): a host plan over the projector's rows, no per-image tensors
+                # mask and labels come to the host BEFORE the tower is launched: splice_plan then runs under the device work
+                am_np = None if attention_mask is None else attention_mask.detach().cpu().numpy()
+                lab_np = None if labels is None else labels.detach().cpu().numpy()
+                merged = self._merged_unsampled(concat_images, split_sizes, image_sizes, images_mask)
+            elif routed is None:
                 feats, split_sizes = self.encode_images(concat_images, input_ids, split_sizes, attention_mask, images_mask, image_sizes,
                                                         labels=labels)
             if type(feats) is not list:
@@ -528,9 +676,6 @@ class SlimeMetaForCausalLM(ABC):
                     flat.append(f[0])
                 elif merge_type == "flat":                                  # :290-291
                     flat.append(f.flatten(0, 1))
-                elif merge_type.startswith("spatial"):
-                    raise NotImplementedError("LLaVA-NeXT style spatial merge of un-sampled crops (llava_arch.py:293-330) is outside "
-                                              "the SliME hot path: SliME merges inside encode_images (sampler branch)")
                 else:
                     raise ValueError(f"Unexpected mm_patch_merge_type: {merge_type}")
             feats = flat
@@ -544,9 +689,12 @@ class SlimeMetaForCausalLM(ABC):
         table = embed.weight
         dev = table.device
         feat_lens = [f.shape[0] for f in feats] if routed is None else [routed[3] + 1 + c for c in routed[5]]
-        src, lab, mask, pos = splice_plan(ids_np,
-                                          None if attention_mask is None else attention_mask.detach().cpu().numpy(),
-                                          None if labels is None else labels.detach().cpu().numpy(),
+        if merged is not None:
+            feat_lens = [int(p.shape[0]) for p in merged[0]]
+        if merged is None:
+            am_np = None if attention_mask is None else attention_mask.detach().cpu().numpy()
+            lab_np = None if labels is None else labels.detach().cpu().numpy()
+        src, lab, mask, pos = splice_plan(ids_np, am_np, lab_np,
                                           feat_lens, getattr(self.config, "tokenizer_model_max_length", None),
                                           getattr(self.config, "tokenizer_padding_side", "right"), vocab_size=vocab)
         B, T = src.shape
@@ -558,6 +706,14 @@ class SlimeMetaForCausalLM(ABC):
             src_d = torch.from_numpy(routed_src(src, feat_lens)).reshape(-1).to(dev)
             new_input_embeds = ops.splice_routed(table.detach(), int(self.config.seperator), tokens, P, st, src_d, concat_images.dtype,
                                                  out_dtype).view(B, T, -1)
+        elif merged is not None:
+            # the same plan looked up in the per-image merge plans: an image row names a row of the projector's fp32 output, a zero
+            # row or image_newline; the projector rows take the rounding encode_images gives its features, then the cast to the table's
+            plans, tokens, mid = merged
+            newline = getattr(self.get_model(), "image_newline", None)
+            extra = None if newline is None else newline.detach()[None].to(dev)
+            src_d = torch.from_numpy(merged_src(src, plans, tokens.shape[0])).reshape(-1).to(dev)
+            new_input_embeds = ops.splice_merged(table.detach(), tokens, extra, src_d, mid, out_dtype).view(B, T, -1)
         else:
             allf = torch.cat([f.reshape(-1, f.shape[-1]) for f in feats], 0).to(dev) if feats else None
             new_input_embeds = ops.splice_rows(table.detach(), allf, torch.from_numpy(src).reshape(-1).to(dev), out_dtype).view(B, T, -1)
@@ -625,6 +781,16 @@ class SlimeVisualEncoder(nn.Module, SlimeMetaForCausalLM):
             self.model.mm_projector.load_state_dict(sub_state(adapter_sd, "mm_projector."), strict=True)
             if len(self.model.sampler.state_dict()) > 0:          # IdentityMap (no sampler) has no parameters
                 self.model.sampler.load_state_dict(sub_state(adapter_sd, "sampler."), strict=True)
+            newline = getattr(self.model, "image_newline", None)
+            if newline is not None:                                # train.py:246 saves it next to mm_projector; optional here
+                for key in ("image_newline", "model.image_newline"):
+                    if key in adapter_sd:
+                        v = adapter_sd[key]
+                        if tuple(v.shape) != tuple(newline.shape):
+                            raise ValueError(f"{key} has shape {tuple(v.shape)}, the model's image_newline {tuple(newline.shape)}")
+                        with torch.no_grad():
+                            newline.copy_(v)
+                        break
         return self
 
     @torch.no_grad()

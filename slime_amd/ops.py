@@ -1309,6 +1309,40 @@ def splice_routed(table: torch.Tensor, sep_id: int, tokens: torch.Tensor, P: int
     return out
 
 
+def splice_merged(table: torch.Tensor, tokens: Optional[torch.Tensor], extra: Optional[torch.Tensor], src: torch.Tensor,
+                  mid_dtype: torch.dtype, out_dtype: torch.dtype) -> torch.Tensor:
+    """``splice_rows`` without the merged per-image features of the un-sampled 'spatial' / 'spatial_unpad' branch: a ``src`` entry
+    ``-2 - k`` names row k of the virtual concatenation ``[tokens | extra]`` -- ``tokens`` fp32 [crops * P, H], the projector's output,
+    whose rows take the value ``x.to(mid_dtype).to(out_dtype)``; ``extra`` [n, H] (``image_newline[None]``), cast once or copied.
+    One launch; returns [src.numel(), H] of ``out_dtype``."""
+    lib = _lib.load()
+    _require_cuda(src, "src")
+    H = table.shape[-1]
+    if tokens is not None and tokens.numel() == 0:
+        tokens = None
+    if extra is not None and extra.numel() == 0:
+        extra = None
+    if tokens is not None:
+        _require_cuda(tokens, "tokens")
+        assert tokens.dim() == 2 and tokens.dtype == torch.float32 and tokens.is_contiguous()
+        assert table.device == tokens.device == src.device, "splice_merged: table, tokens and src live on one device"
+        assert tokens.shape[1] == H, f"embedding rows of {H}, token rows of {tokens.shape[1]}"
+    if extra is not None:
+        _require_cuda(extra, "extra")
+        assert extra.dim() == 2 and extra.shape[1] == H, f"embedding rows of {H}, extra rows of {tuple(extra.shape)}"
+        assert extra.device == src.device, "splice_merged: extra and src live on one device"
+        extra = extra.contiguous()
+    assert table.device == src.device, "splice_merged: table and src live on one device"
+    rows = src.numel()
+    out = torch.empty((rows, H), dtype=out_dtype, device=src.device)
+    t = table.contiguous()
+    _lib.check(lib.slime_splice_merged(_ptr(t), dtype_code(t.dtype), t.shape[0], _ptr(tokens), 0 if tokens is None else tokens.shape[0],
+                                       dtype_code(mid_dtype), _ptr(extra), dtype_code(extra.dtype) if extra is not None else 0,
+                                       0 if extra is None else extra.shape[0], _ptr(src.contiguous()), out.data_ptr(),
+                                       dtype_code(out_dtype), rows, H, _stream()), "slime_splice_merged")
+    return out
+
+
 @dataclass
 class PackedLlamaAttention:
     hidden: int
