@@ -569,7 +569,10 @@ int slime_gated_forward(const slime_mlp_desc* mlp, const slime_resampler_desc* a
  *          rows [576, 576 + n_local*g*g) = merged local tokens (raster order if merge != 0; nw*nh == n_local).
  * projection[2] stores every row straight into `out` (slime_gemm_args.row_map) when out_dtype is fp32 or the operand type T;
  * a 16-bit out_dtype OTHER than T (bf16 tokens from an fp16 adapter or vice versa) takes fp32 rows + slime_merge_rows_batched
- * instead: same values, two more passes over the token rows. */
+ * instead: same values, two more passes over the token rows.
+ * Every argument check (SLIME_EINVAL with the limit named: descriptors that do not fit each other, a grid that does not hold n_local,
+ * out_image_stride smaller than an image's rows, n_images * out_image_stride >= 2^31 for the direct store; SLIME_EWORKSPACE) precedes
+ * the first launch: a refused call writes neither `out` nor the workspace. */
 size_t slime_adapter_workspace_bytes(const slime_mlp_desc* mlp, const slime_resampler_desc* attn,
                                      const slime_resampler_desc* post, int n_images, int n_local);
 int slime_adapter_forward(const slime_mlp_desc* mlp, const slime_resampler_desc* attn, const float* w_gate,

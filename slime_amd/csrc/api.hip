@@ -542,6 +542,9 @@ extern "C" int slime_adapter_forward(const slime_mlp_desc* mlp, const slime_resa
     const int P = attn->n_kv, D = mlp->in_dim, H = mlp->hidden, dt = mlp->dtype;
     const AdapterPlan p = adapter_plan(mlp, attn, post, n_images, n_local, learnable_gated);
     SLIME_REQUIRE(out_image_stride >= P + (long)n_local * (post ? post->n_query : 0), "adapter: out_image_stride %ld too small", out_image_stride);
+    // (the direct store's limit; checked here, with every other argument, before the first launch)
+    const bool direct = out_dtype == SLIME_F32 || out_dtype == dt;
+    SLIME_REQUIRE(!direct || (long)n_images * out_image_stride < (1L << 31), "adapter: token buffer too large for the 32-bit row map");
     if (!ws || ws_bytes < p.total || ((uintptr_t)ws % 256) != 0) {
         slime_set_error("adapter: workspace %zu B (need %zu, 256-B aligned)", ws_bytes, p.total);
         return SLIME_EWORKSPACE;
@@ -582,10 +585,8 @@ extern "C" int slime_adapter_forward(const slime_mlp_desc* mlp, const slime_resa
     // passes (two launches, 151 MB written + read back per 8 x (1+4) step).  The same values, rounded once by the same RNE pack as the
     // merge kernel's: bit-identical to the per-module sequence.  Other output dtypes (a 16-bit type that is not the operand type) keep
     // the fp32 rows + merge path.
-    const bool direct = out_dtype == SLIME_F32 || out_dtype == dt;
     int* rmap = (int*)(w + p.rmap);
     if (direct) {
-        SLIME_REQUIRE((long)n_images * out_image_stride < (1L << 31), "adapter: token buffer too large for the 32-bit row map");
         TRY(adapter_row_map_launch(rmap, p.rows_g, P, p.rows_l, post ? (long)n_local * post->n_query : 1, g > 0 ? g : 1, nw > 0 ? nw : 1, merge,
                                    out_image_stride, stream));
     }

@@ -306,7 +306,7 @@ def test_fused_adapter_equals_module_sequence(dev, dtype, gated):
     # 16-bit output into a wider token buffer: rows beyond the image's tokens stay untouched
     wide = torch.full((B, ref.shape[1] + 5, 256), 3.0, dtype=dtype, device=dev)
     ops.adapter_forward(pg, post, feats, B, n_local, nw, nh, True, gated, out=wide)
-    assert torch.equal(wide[:, :ref.shape[1]], ref.to(dtype)) or rel_l2(wide[:, :ref.shape[1]].float().cpu(), ref.cpu()) < 2e-3
+    assert torch.equal(wide[:, :ref.shape[1]], ref.to(dtype))     # the direct store rounds once, by the merge kernel's RNE pack
     assert bool((wide[:, ref.shape[1]:] == 3.0).all())
     # flat order and a global-only batch
     flat = ops.adapter_forward(pg, post, feats, B, n_local, n_local, 1, False, gated, torch.float32)
