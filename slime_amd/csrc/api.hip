@@ -49,6 +49,13 @@ namespace {
 static bool is16(int dt) { return dt == SLIME_BF16 || dt == SLIME_F16; }
 }  // namespace
 
+// every driver's workspace: `need` bytes at a 256-B aligned address
+static int ws_check(const char* name, const void* ws, size_t ws_bytes, size_t need) {
+    if (ws && ws_bytes >= need && ((uintptr_t)ws % 256) == 0) return SLIME_OK;
+    slime_set_error("%s: workspace %zu B (need %zu, 256-B aligned)", name, ws_bytes, need);
+    return SLIME_EWORKSPACE;
+}
+
 // ------------------------------------------------------------------------------------------------
 // CLIP tower
 // ------------------------------------------------------------------------------------------------
@@ -194,10 +201,7 @@ static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, i
     if (ks) TRY(vit_ksplit_validate(d, ks));
     const VitPlan p = vit_plan(d, n);
     const size_t part_bytes = ks ? vit_ksplit_partial_bytes(d, n, ks) : 0;      // one region of partial products behind the plan
-    if (!ws || ws_bytes < p.total + part_bytes || ((uintptr_t)ws % 256) != 0) {
-        slime_set_error("vit: workspace %zu B (need %zu, 256-B aligned)", ws_bytes, p.total + part_bytes);
-        return SLIME_EWORKSPACE;
-    }
+    TRY(ws_check("vit", ws, ws_bytes, p.total + part_bytes));
     // a layer GEMM: slime_gemm_ex, or the split pair where the caller asked for one (the probe brackets the GEMM as a whole)
     auto layer_gemm = [&](const slime_gemm_args& a, int splits) {
         return splits > 1 ? slime_gemm_ksplit(&a, splits, (char*)ws + p.total, part_bytes, stream) : slime_gemm_ex(&a, stream);
@@ -318,20 +322,18 @@ extern "C" size_t slime_resampler_workspace_bytes(const slime_resampler_desc* d,
 int layernorm_crops_launch(const void* feats, int dtype, int P, int period, int first, int per_image, int images, int D, const float* w,
                            const float* b, float eps, void* out_t, void* out_t2, const float* add, int add_period, void* stream);   // rowwise.hip (internal)
 
-// crops != nullptr (fused adapter, round 5): the input rows are the selected crops of the tower's T features, read by the first
-// LayerNorm directly (no fp32 copy of them); otherwise x fp32 [n, n_kv, dim]
-// (table != nullptr, ragged fused adapter: crop j of the n input crops is feats crop table[j], a DEVICE int32 array)
+// A crop source of the fused adapter: crop j of the n selected crops is crop (j / per_image) * period + first + j % per_image of the
+// tower's T features (a uniform batch), or crop table[j] (table != nullptr, a DEVICE int32 array: the ragged batch)
 struct ResCrops { const void* feats; int period, first, per_image, images; const int* table = nullptr; };
+// crops != nullptr (fused adapter, round 5): the input rows are those crops, read by the first LayerNorm directly (no fp32 copy of
+// them); otherwise x fp32 [n, n_kv, dim]
 static int resampler_run(const slime_resampler_desc* d, const float* x, int ldx, const ResCrops* crops, int n, float* out_f32,
                          void* out_t, void* ws, size_t ws_bytes, void* stream) {
     TRY(resampler_validate(d));
     SLIME_REQUIRE((x || crops) && n > 0 && (crops || ldx >= d->dim), "resampler: bad input");
     SLIME_REQUIRE(out_f32 || out_t, "resampler: no output requested");
     const ResPlan p = res_plan(d, n);
-    if (!ws || ws_bytes < p.total || ((uintptr_t)ws % 256) != 0) {
-        slime_set_error("resampler: workspace %zu B (need %zu, 256-B aligned)", ws_bytes, p.total);
-        return SLIME_EWORKSPACE;
-    }
+    TRY(ws_check("resampler", ws, ws_bytes, p.total));
     char* w = (char*)ws;
     const int D = d->dim, Rk = n * d->n_kv, Rq = n * d->n_query, dh = D / d->heads, dt = d->dtype;
     // x = ln_kv(x); K input = x + pos (sampler.py:158,164); V input = x
@@ -393,10 +395,7 @@ extern "C" int slime_mlp_forward(const slime_mlp_desc* d, const float* x_f32, co
     TRY(mlp_validate(d));
     SLIME_REQUIRE((x_f32 || x_t) && out && rows > 0, "mlp: bad input");
     const MlpPlan p = mlp_plan(d, rows);
-    if (!ws || ws_bytes < p.total || ((uintptr_t)ws % 256) != 0) {
-        slime_set_error("mlp: workspace %zu B (need %zu, 256-B aligned)", ws_bytes, p.total);
-        return SLIME_EWORKSPACE;
-    }
+    TRY(ws_check("mlp", ws, ws_bytes, p.total));
     char* w = (char*)ws;
     const void* a = x_t;
     if (!a) {
@@ -433,6 +432,32 @@ extern "C" size_t slime_gated_workspace_bytes(const slime_mlp_desc* mlp, const s
     return gated_plan(mlp, attn, n).total;
 }
 
+// Both experts, mixed by the gate (builder.py:190-206).  projection[0] + GELU run over the stacked rows [T(x) | attn(x) | local rows]
+// (row offsets seg_x = 0, seg_attn, seg_local; seg_local < 0: no local rows); the gate, from the fp32 global rows x32, mixes the
+// HIDDEN rows of the two global segments into the second one (slime_gate_premix: projection[2] is linear and g0 + g1 =
+// 1 / (1 + 1e-6)), so projection[2] runs over ONE row per token -- a third less GEMM work than two complete experts (round 4).
+// Returns projection[2]'s A operand, the [mixed global | local] rows of `mid`, and its row count.
+static int both_experts_hidden(const slime_mlp_desc* mlp, const float* w_gate, const char* stack, long seg_x, long seg_attn, long seg_local,
+                               long rows_g, long rows_l, const float* x32, float* gates, char* mid, void* stream, const void** a2, int* rows2) {
+    const int D = mlp->in_dim, H = mlp->hidden, dt = mlp->dtype;
+    char* mixed = mid + (size_t)seg_attn * H * 2;
+    if (mix_in_gemm(mlp)) {
+        // the mix in fp32 inside projection[0]'s epilogue (SLIME_EPI_BIAS_GELU_MIX_T: one rounding, no pass over the hidden rows,
+        // half the global hidden rows written); the local rows follow in their own launch, directly behind the mixed rows
+        TRY(slime_gate_weights(x32, D, w_gate, gates, (int)rows_g, stream));
+        TRY(gemm_mix(stack + (size_t)seg_x * D * 2, stack + (size_t)seg_attn * D * 2, gates, mlp, mixed, (int)rows_g, stream));
+        if (seg_local >= 0)
+            TRY(gemm_w(stack + (size_t)seg_local * D * 2, D, mlp->w1, mlp->w1_frag, mlp->b1, mid + (size_t)seg_local * H * 2, H,
+                       (int)rows_l, H, D, dt, SLIME_EPI_BIAS_GELU_T, stream));
+    } else {
+        TRY(gemm_w(stack, D, mlp->w1, mlp->w1_frag, mlp->b1, mid, H, (int)(2 * rows_g + rows_l), H, D, dt, SLIME_EPI_BIAS_GELU_T, stream));
+        TRY(slime_gate_premix(x32, D, w_gate, mid + (size_t)seg_x * H * 2, mixed, mixed, dt, (int)rows_g, H, stream));
+    }
+    *a2 = mixed;
+    *rows2 = (int)(rows_g + rows_l);
+    return SLIME_OK;
+}
+
 extern "C" int slime_gated_forward(const slime_mlp_desc* mlp, const slime_resampler_desc* attn, const float* w_gate,
                                    int learnable_gated, const float* x, int n, float* out, void* ws, size_t ws_bytes,
                                    void* stream) {
@@ -443,10 +468,7 @@ extern "C" int slime_gated_forward(const slime_mlp_desc* mlp, const slime_resamp
     SLIME_REQUIRE(learnable_gated >= 0 || w_gate, "gated: missing w_gate");
     SLIME_REQUIRE(learnable_gated <= 1, "gated: expert index %d", learnable_gated);
     const GatedPlan p = gated_plan(mlp, attn, n);
-    if (!ws || ws_bytes < p.total || ((uintptr_t)ws % 256) != 0) {
-        slime_set_error("gated: workspace %zu B (need %zu, 256-B aligned)", ws_bytes, p.total);
-        return SLIME_EWORKSPACE;
-    }
+    TRY(ws_check("gated", ws, ws_bytes, p.total));
     char* w = (char*)ws;
     const int rows = n * attn->n_query, D = mlp->in_dim, H = mlp->hidden, dt = mlp->dtype;
     const MlpPlan mp = mlp_plan(mlp, 2 * rows);
@@ -458,22 +480,12 @@ extern "C" int slime_gated_forward(const slime_mlp_desc* mlp, const slime_resamp
     TRY(slime_resampler_forward(attn, x, attn->dim, n, nullptr, attn_t, w + p.res, res_ws, stream));
     if (learnable_gated == 1)                                   // expert 1: projection(attn(x))
         return slime_mlp_forward(mlp, nullptr, attn_t, rows, out, w + p.mlp, mp.total, stream);
-    // Both experts, mixed by the gate (builder.py:190-206).  projection[0] + GELU run over the stacked rows [T(x) | attn(x)]; the gate
-    // mixes the HIDDEN rows (slime_gate_premix: projection[2] is linear and g0 + g1 = 1 / (1 + 1e-6)), so projection[2] runs over ONE
-    // row per token and writes the block's output directly -- a third less GEMM work than two complete experts (round 4).
-    char* mid = w + p.mlp + mp.mid;
-    char* mixed = mid + (size_t)rows * H * 2;
+    // both experts: the block's output is projection[2] over the mixed hidden rows
+    const void* a2;
+    int rows2;
     TRY(slime_layernorm(x, D, rows, D, nullptr, nullptr, 0.f, 0, nullptr, stack, nullptr, nullptr, 0, dt, stream));
-    if (mix_in_gemm(mlp)) {
-        // the mix in fp32 inside projection[0]'s epilogue (one rounding, no pass over the hidden rows): SLIME_EPI_BIAS_GELU_MIX_T
-        float* gates = (float*)(w + p.gates);
-        TRY(slime_gate_weights(x, D, w_gate, gates, rows, stream));
-        TRY(gemm_mix(stack, attn_t, gates, mlp, mixed, rows, stream));
-    } else {
-        TRY(gemm_w(stack, D, mlp->w1, mlp->w1_frag, mlp->b1, mid, H, 2 * rows, H, D, dt, SLIME_EPI_BIAS_GELU_T, stream));
-        TRY(slime_gate_premix(x, D, w_gate, mid, mixed, mixed, dt, rows, H, stream));
-    }
-    TRY(gemm_w(mixed, H, mlp->w2, mlp->w2_frag, mlp->b2, out, H, rows, H, H, dt, SLIME_EPI_BIAS_F32, stream));
+    TRY(both_experts_hidden(mlp, w_gate, stack, 0, rows, -1, rows, 0, x, (float*)(w + p.gates), w + p.mlp + mp.mid, stream, &a2, &rows2));
+    TRY(gemm_w(a2, H, mlp->w2, mlp->w2_frag, mlp->b2, out, H, rows2, H, H, dt, SLIME_EPI_BIAS_F32, stream));
     return SLIME_OK;
 }
 
@@ -482,20 +494,30 @@ extern "C" int slime_gated_forward(const slime_mlp_desc* mlp, const slime_resamp
 // ------------------------------------------------------------------------------------------------
 int adapter_row_map_launch(int* map, long rows_g, int P, long rows_l, long per_image_local, int g, int nw, int merge, long out_image_stride,
                            void* stream);                                   // rowwise.hip (internal)
-struct AdapterPlan { size_t xg32, xl32, stack, e, mlp, res, gates, rmap, total; long rows_g, rows_l, rows_all; int segs_g; };
+struct AdapterPlan {
+    size_t xg32, stack, e, mlp, res, gates, rmap, total;    // offsets
+    long rows_g, rows_l, rows_all, total_local;
+    int n_images, segs_g;
+    long seg_x, seg_attn, seg_local;                        // first row of each segment of the stack (-1: dropped)
+};
 // total_local = local crops of the whole batch (n_images * n_local for a uniform batch, sum n_i for a ragged one)
 static AdapterPlan adapter_plan_total(const slime_mlp_desc* m, const slime_resampler_desc* attn, const slime_resampler_desc* post,
                                       int n_images, long total_local, int learnable_gated) {
     AdapterPlan p{};
     const size_t D = m->in_dim, H = m->hidden;
+    p.n_images = n_images;
+    p.total_local = total_local;
     p.rows_g = (long)n_images * attn->n_kv;
     p.rows_l = post ? total_local * post->n_query : 0;
     p.segs_g = learnable_gated < 0 ? 2 : 1;
     p.rows_all = p.segs_g * p.rows_g + p.rows_l;
+    // stacked MLP input: [x_global | attn(x_global) | post_qformer(x_local)] (segments that are not needed are dropped)
+    p.seg_x = learnable_gated != 1 ? 0 : -1;
+    p.seg_attn = learnable_gated != 0 ? (p.segs_g - 1) * p.rows_g : -1;
+    p.seg_local = post ? p.segs_g * p.rows_g : -1;
     size_t off = 0;
     auto take = [&](size_t b) { size_t o = align_up(off, 256); off = o + b; return o; };
     p.xg32 = take((size_t)p.rows_g * D * 4);
-    p.xl32 = take(0);                 // (round 5: the local crops' fp32 copy is gone -- post_qformer's LayerNorm reads the T features)
     p.stack = take((size_t)p.rows_all * D * 2);
     p.e = take((size_t)p.rows_all * H * 4);
     p.mlp = take(mlp_plan(m, (int)p.rows_all).total);
@@ -518,128 +540,126 @@ extern "C" size_t slime_adapter_workspace_bytes(const slime_mlp_desc* mlp, const
     return adapter_plan(mlp, attn, n_local > 0 ? post : nullptr, n_images, n_local, -1).total;
 }
 
-extern "C" int slime_adapter_forward(const slime_mlp_desc* mlp, const slime_resampler_desc* attn, const float* w_gate,
-                                     int learnable_gated, const slime_resampler_desc* post, const void* feats,
-                                     int n_images, int n_local, int nw, int nh, int merge, void* out, int out_dtype,
-                                     long out_image_stride, void* ws, size_t ws_bytes, void* stream) {
+// The checks the uniform and the ragged entry share (`who`: the entry's own prefix, for its bad-input message)
+static int adapter_validate(const slime_mlp_desc* mlp, const slime_resampler_desc* attn, const float* w_gate, int learnable_gated,
+                            bool args_ok, const char* who) {
     TRY(mlp_validate(mlp));
     TRY(resampler_validate(attn));
-    SLIME_REQUIRE(feats && out && n_images > 0 && n_local >= 0, "adapter: bad input");
+    SLIME_REQUIRE(args_ok, "%s: bad input", who);
     SLIME_REQUIRE(attn->dim == mlp->in_dim && attn->n_query == attn->n_kv, "adapter: attn must map the token grid onto itself");
     SLIME_REQUIRE(learnable_gated >= 0 || w_gate, "adapter: missing w_gate");
     SLIME_REQUIRE(learnable_gated <= 1, "adapter: expert index %d", learnable_gated);
     SLIME_REQUIRE(attn->dtype == mlp->dtype, "adapter: mixed operand dtypes");
-    int g = 0;
+    return SLIME_OK;
+}
+// ... and, where the batch has local crops, post_qformer against the tower grid; *g = the side of its square query grid
+static int adapter_validate_post(const slime_mlp_desc* mlp, const slime_resampler_desc* attn, const slime_resampler_desc* post, int* g) {
+    TRY(resampler_validate(post));
+    SLIME_REQUIRE(post->dim == mlp->in_dim && post->n_kv == attn->n_kv && post->dtype == mlp->dtype, "adapter: post_qformer does not match the tower grid");
+    int s = 0;
+    while (s * s < post->n_query) ++s;
+    SLIME_REQUIRE(s * s == post->n_query, "adapter: post_qformer query count %d is not a square grid", post->n_query);
+    *g = s;
+    return SLIME_OK;
+}
+
+// The adapter's launch sequence, the one body behind slime_adapter_forward and slime_adapter_forward_ragged: global crop select ->
+// attn resampler -> post_qformer on the local crops -> projection[0] over the stack (with the gate mix where both experts run) ->
+// projection[2].  `glob` / `local` say where a crop's features come from (window arithmetic or a device table).  projection[2]
+// stores every row straight into the token buffer `out` through `row_map` (round 5; slime_gemm_args.row_map: global rows to rows
+// [0, P) of their image, local rows to their raster position behind them), rounded once by the same RNE pack as the merge kernel's:
+// bit-identical to the per-module sequence.  row_map == nullptr: plain [global | local] rows to `out`, for the caller to merge.
+// `uniform` != nullptr: row_map is still to be built, by adapter_row_map_launch from these numbers, where the uniform call has always
+// launched it -- behind the resamplers (a ragged batch's plan kernel, which also writes the crop tables, has to run before the body).
+struct UniformRows { long per_image_local, out_image_stride; int g, nw, merge; };
+static int adapter_run(const slime_mlp_desc* mlp, const slime_resampler_desc* attn, const float* w_gate, const slime_resampler_desc* post,
+                       const AdapterPlan& p, char* w, const ResCrops& glob, const ResCrops& local, const UniformRows* uniform, int* row_map,
+                       void* out, int out_dtype, void* stream) {
+    const int P = attn->n_kv, D = mlp->in_dim, H = mlp->hidden, dt = mlp->dtype;
+    float* xg32 = (float*)(w + p.xg32);
+    char* stack = w + p.stack;
+    auto seg = [&](long s) { return stack + (size_t)s * D * 2; };
+    // global crops: fp32 copy for the resampler's LayerNorm and the gate logits, T copy straight into the stack
+    void* x_t = p.seg_x >= 0 ? seg(p.seg_x) : nullptr;
+    if (glob.table)
+        TRY(select_crops_indexed_launch(glob.feats, dt, P, D, glob.table, p.n_images, xg32, x_t, stream));
+    else
+        TRY(slime_select_crops(glob.feats, dt, P, D, glob.period, glob.first, glob.per_image, glob.images, xg32, x_t, stream));
+    if (p.seg_attn >= 0)
+        TRY(slime_resampler_forward(attn, xg32, D, p.n_images, nullptr, seg(p.seg_attn), w + p.res, res_plan(attn, p.n_images).total, stream));
+    if (post)
+        // local crops: post_qformer's first LayerNorm reads them straight from the tower's T features (round 5: no fp32 copy --
+        // 75 MB written and read back per 8 x (1+4) step --, no select_crops launch; float(T) either way: bit-identical)
+        TRY(resampler_run(post, nullptr, 0, &local, (int)p.total_local, nullptr, seg(p.seg_local), w + p.res,
+                          res_plan(post, (int)p.total_local).total, stream));
+    if (uniform)
+        TRY(adapter_row_map_launch(row_map, p.rows_g, P, p.rows_l, uniform->per_image_local, uniform->g, uniform->nw, uniform->merge,
+                                   uniform->out_image_stride, stream));
+    // projection MLP over the stack: projection[2] runs over one row per output token, [mixed global | local] with both experts
+    char* mid = w + p.mlp + mlp_plan(mlp, (int)p.rows_all).mid;
+    const void* a2 = mid;
+    int rows2 = (int)p.rows_all;
+    if (p.segs_g == 2)
+        TRY(both_experts_hidden(mlp, w_gate, stack, p.seg_x, p.seg_attn, p.seg_local, p.rows_g, p.rows_l, xg32, (float*)(w + p.gates), mid,
+                                stream, &a2, &rows2));
+    else
+        TRY(gemm_w(stack, D, mlp->w1, mlp->w1_frag, mlp->b1, mid, H, rows2, H, D, dt, SLIME_EPI_BIAS_GELU_T, stream));
+    slime_gemm_args a{};
+    a.A = a2; a.lda = H; a.B = mlp->w2; a.B_frag = mlp->w2_frag; a.bias = mlp->b2; a.M = rows2; a.N = H; a.K = H; a.dtype = dt;
+    a.C = out; a.ldc = H; a.row_map = row_map; a.epilogue = out_dtype == SLIME_F32 ? SLIME_EPI_BIAS_F32 : SLIME_EPI_BIAS_T;
+    return slime_gemm_ex(&a, stream);
+}
+
+// A batch whose images share one crop layout (1 global + n_local = nw x nh local crops each)
+extern "C" int slime_adapter_forward(const slime_mlp_desc* mlp, const slime_resampler_desc* attn, const float* w_gate,
+                                     int learnable_gated, const slime_resampler_desc* post, const void* feats,
+                                     int n_images, int n_local, int nw, int nh, int merge, void* out, int out_dtype,
+                                     long out_image_stride, void* ws, size_t ws_bytes, void* stream) {
+    TRY(adapter_validate(mlp, attn, w_gate, learnable_gated, feats && out && n_images > 0 && n_local >= 0, "adapter"));
+    int g = 1;
     if (n_local > 0) {
-        TRY(resampler_validate(post));
-        SLIME_REQUIRE(post->dim == mlp->in_dim && post->n_kv == attn->n_kv && post->dtype == mlp->dtype, "adapter: post_qformer does not match the tower grid");
-        while (g * g < post->n_query) ++g;
-        SLIME_REQUIRE(g * g == post->n_query, "adapter: post_qformer query count %d is not a square grid", post->n_query);
+        TRY(adapter_validate_post(mlp, attn, post, &g));
         SLIME_REQUIRE(nw > 0 && nh > 0 && nw * nh == n_local, "adapter: grid %dx%d does not hold %d local crops", nw, nh, n_local);
     } else {
         post = nullptr;
     }
-    const int P = attn->n_kv, D = mlp->in_dim, H = mlp->hidden, dt = mlp->dtype;
+    const int P = attn->n_kv, H = mlp->hidden;
+    const long per_image_local = post ? (long)n_local * post->n_query : 0;
     const AdapterPlan p = adapter_plan(mlp, attn, post, n_images, n_local, learnable_gated);
-    SLIME_REQUIRE(out_image_stride >= P + (long)n_local * (post ? post->n_query : 0), "adapter: out_image_stride %ld too small", out_image_stride);
+    SLIME_REQUIRE(out_image_stride >= P + per_image_local, "adapter: out_image_stride %ld too small", out_image_stride);
     // (the direct store's limit; checked here, with every other argument, before the first launch)
-    const bool direct = out_dtype == SLIME_F32 || out_dtype == dt;
+    const bool direct = out_dtype == SLIME_F32 || out_dtype == mlp->dtype;
     SLIME_REQUIRE(!direct || (long)n_images * out_image_stride < (1L << 31), "adapter: token buffer too large for the 32-bit row map");
-    if (!ws || ws_bytes < p.total || ((uintptr_t)ws % 256) != 0) {
-        slime_set_error("adapter: workspace %zu B (need %zu, 256-B aligned)", ws_bytes, p.total);
-        return SLIME_EWORKSPACE;
-    }
+    TRY(ws_check("adapter", ws, ws_bytes, p.total));
     char* w = (char*)ws;
-    float* xg32 = (float*)(w + p.xg32);
-    char* stack = w + p.stack;
-    float* e = (float*)(w + p.e);
-    const int period = 1 + n_local;
-
-    // stacked MLP input: [x_global | attn(x_global) | post_qformer(x_local)] (segments that are not needed are dropped)
-    size_t row = 0;
-    long seg_x = -1, seg_attn = -1, seg_local = -1;
-    if (learnable_gated != 1) { seg_x = (long)row; row += p.rows_g; }
-    if (learnable_gated != 0) { seg_attn = (long)row; row += p.rows_g; }
-    if (post) { seg_local = (long)row; row += p.rows_l; }
-
-    // global crops: fp32 copy for the resampler's LayerNorm and the gate logits, T copy straight into the stack
-    TRY(slime_select_crops(feats, dt, P, D, period, 0, 1, n_images, xg32, seg_x >= 0 ? stack + (size_t)seg_x * D * 2 : nullptr, stream));
-    if (seg_attn >= 0)
-        TRY(slime_resampler_forward(attn, xg32, D, n_images, nullptr, stack + (size_t)seg_attn * D * 2, w + p.res,
-                                    res_plan(attn, n_images).total, stream));
-    if (post) {
-        // local crops: post_qformer's first LayerNorm reads them straight from the tower's T features (round 5: no fp32 copy --
-        // 75 MB written and read back per 8 x (1+4) step --, no select_crops launch; float(T) either way: bit-identical)
-        const ResCrops rc{feats, period, 1, n_local, n_images};
-        TRY(resampler_run(post, nullptr, 0, &rc, n_images * n_local, nullptr, stack + (size_t)seg_local * D * 2, w + p.res,
-                          res_plan(post, n_images * n_local).total, stream));
-    }
-    // projection MLP over the stack.  With both experts (learnable_gated < 0) the gate mixes the HIDDEN rows of the two global
-    // segments (slime_gate_premix, into the second one) and projection[2] runs over [mixed global | local] = one row per output
-    // token; e then holds [global | local] rows.  Otherwise e holds the stack's rows.
-    const MlpPlan mp = mlp_plan(mlp, (int)p.rows_all);
-    char* mid = w + p.mlp + mp.mid;
-    long e_glob = 0, e_local = seg_local;                       // rows of e
-    // Round 5: projection[2] stores every output row straight into the token buffer (slime_gemm_args.row_map: global rows to rows
-    // [0, P) of their image, local rows to their raster position behind them) in the output dtype -- no fp32 rows `e`, no merge
-    // passes (two launches, 151 MB written + read back per 8 x (1+4) step).  The same values, rounded once by the same RNE pack as the
-    // merge kernel's: bit-identical to the per-module sequence.  Other output dtypes (a 16-bit type that is not the operand type) keep
-    // the fp32 rows + merge path.
-    int* rmap = (int*)(w + p.rmap);
+    const ResCrops glob{feats, 1 + n_local, 0, 1, n_images}, local{feats, 1 + n_local, 1, n_local, n_images};
     if (direct) {
-        TRY(adapter_row_map_launch(rmap, p.rows_g, P, p.rows_l, post ? (long)n_local * post->n_query : 1, g > 0 ? g : 1, nw > 0 ? nw : 1, merge,
-                                   out_image_stride, stream));
+        const UniformRows rows{post ? per_image_local : 1, out_image_stride, g, nw > 0 ? nw : 1, merge};
+        return adapter_run(mlp, attn, w_gate, post, p, w, glob, local, &rows, (int*)(w + p.rmap), out, out_dtype, stream);
     }
-    auto projection2 = [&](const void* A, int rows) -> int {     // rows = [global | local] rows of the hidden activations
-        slime_gemm_args a{};
-        a.A = A; a.lda = H; a.B = mlp->w2; a.B_frag = mlp->w2_frag; a.bias = mlp->b2; a.M = rows; a.N = H; a.K = H; a.dtype = dt;
-        if (direct) { a.C = out; a.ldc = H; a.row_map = rmap; a.epilogue = out_dtype == SLIME_F32 ? SLIME_EPI_BIAS_F32 : SLIME_EPI_BIAS_T; }
-        else { a.C = e; a.ldc = H; a.epilogue = SLIME_EPI_BIAS_F32; }
-        return slime_gemm_ex(&a, stream);
-    };
-    if (learnable_gated < 0) {
-        char* mixed = mid + (size_t)seg_attn * H * 2;
-        if (mix_in_gemm(mlp)) {
-            // the mix in fp32 inside projection[0]'s epilogue (SLIME_EPI_BIAS_GELU_MIX_T: one rounding, no pass over the hidden rows,
-            // half the global hidden rows written); the local rows follow in their own launch, directly behind the mixed rows
-            float* gates = (float*)(w + p.gates);
-            TRY(slime_gate_weights(xg32, D, w_gate, gates, (int)p.rows_g, stream));
-            TRY(gemm_mix(stack + (size_t)seg_x * D * 2, stack + (size_t)seg_attn * D * 2, gates, mlp, mixed, (int)p.rows_g, stream));
-            if (post)
-                TRY(gemm_w(stack + (size_t)seg_local * D * 2, D, mlp->w1, mlp->w1_frag, mlp->b1, mid + (size_t)seg_local * H * 2, H,
-                           (int)p.rows_l, H, D, dt, SLIME_EPI_BIAS_GELU_T, stream));
-        } else {
-            TRY(gemm_w(stack, D, mlp->w1, mlp->w1_frag, mlp->b1, mid, H, (int)p.rows_all, H, D, dt, SLIME_EPI_BIAS_GELU_T, stream));
-            TRY(slime_gate_premix(xg32, D, w_gate, mid + (size_t)seg_x * H * 2, mixed, mixed, dt, (int)p.rows_g, H, stream));
-        }
-        TRY(projection2(mixed, (int)(p.rows_g + p.rows_l)));
-        e_local = p.rows_g;
-    } else {
-        TRY(gemm_w(stack, D, mlp->w1, mlp->w1_frag, mlp->b1, mid, H, (int)p.rows_all, H, D, dt, SLIME_EPI_BIAS_GELU_T, stream));
-        TRY(projection2(mid, (int)p.rows_all));
-    }
-    if (!direct) {
-        // global tokens -> rows [0, P) of every image: flat cast-copy of P rows per image (nw = P, nh = g = 1, merge = 0)
-        TRY(slime_merge_rows_batched(e + (size_t)e_glob * H, P, out, out_dtype, out_image_stride, 0, n_images, P, 1, 1, H, 0, stream));
-        if (post)
-            TRY(slime_merge_rows_batched(e + (size_t)e_local * H, (long)n_local * post->n_query, out, out_dtype, out_image_stride, P,
-                                         n_images, nw, nh, g, H, merge, stream));
-    }
+    // A 16-bit output type that is not the operand type keeps the fp32 rows e = [global | local] and the merge passes.
+    float* e = (float*)(w + p.e);
+    TRY(adapter_run(mlp, attn, w_gate, post, p, w, glob, local, nullptr, nullptr, e, SLIME_F32, stream));
+    // global tokens -> rows [0, P) of every image: flat cast-copy of P rows per image (nw = P, nh = g = 1, merge = 0)
+    TRY(slime_merge_rows_batched(e, P, out, out_dtype, out_image_stride, 0, n_images, P, 1, 1, H, 0, stream));
+    if (post)
+        TRY(slime_merge_rows_batched(e + (size_t)p.rows_g * H, per_image_local, out, out_dtype, out_image_stride, P, n_images, nw, nh, g, H,
+                                     merge, stream));
     return SLIME_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
-// Fused adapter for a batch whose images have DIFFERENT crop layouts: the sequence of slime_adapter_forward with the three places
-// that assumed one layout -- the crops' positions in feats, the rows each image owns in the token buffer, its crop grid -- read
-// from device tables that ONE plan kernel derives from the per-image layout in its kernel arguments.  Every other launch is the
-// uniform call's (resampler_run, gemm_mix / gemm_w, slime_gate_weights / slime_gate_premix, slime_gemm_ex with row_map); the rows
-// are independent, so an image's tokens are those of the uniform call on that image alone up to the GEMM's tile choice.
+// Fused adapter for a batch whose images have DIFFERENT crop layouts: a second front end of adapter_run.  The three places that
+// assume one layout -- the crops' positions in feats, the rows each image owns in the token buffer, its crop grid -- are read from
+// device tables that ONE plan kernel derives from the per-image layout in its kernel arguments: the two crop tables are adapter_run's
+// crop sources, the third its row map.  Every launch after the plan kernel is the shared body's; the rows are independent, so an
+// image's tokens are those of the uniform call on that image alone up to the GEMM's tile choice.
 // ------------------------------------------------------------------------------------------------
-struct RaggedPlan { AdapterPlan a; size_t gtab, ltab, total; long total_local; };
+struct RaggedPlan { AdapterPlan a; size_t gtab, ltab, total; };
 
 // host-only: validates the grids and fills the layout (out_row0 == nullptr: packed); *post is cleared when no image has local crops
-static int ragged_layout(const slime_resampler_desc* attn, const slime_resampler_desc** post, int n_images, const int* nw, const int* nh,
-                         int merge, const long long* out_row0, long out_rows, RaggedLayout* L) {
+static int ragged_layout(const slime_mlp_desc* mlp, const slime_resampler_desc* attn, const slime_resampler_desc** post, int n_images,
+                         const int* nw, const int* nh, int merge, const long long* out_row0, long out_rows, RaggedLayout* L) {
     SLIME_REQUIRE(n_images > 0 && nw && nh, "adapter_ragged: bad input");
     SLIME_REQUIRE(n_images <= SLIME_ADAPTER_RAGGED_MAX_IMAGES, "adapter_ragged: %d images, more than SLIME_ADAPTER_RAGGED_MAX_IMAGES = %d (the layout "
                   "travels in the kernel arguments)", n_images, SLIME_ADAPTER_RAGGED_MAX_IMAGES);
@@ -653,11 +673,8 @@ static int ragged_layout(const slime_resampler_desc* attn, const slime_resampler
     int g = 1, q = 1;
     if (total_local > 0) {
         SLIME_REQUIRE(*post, "adapter_ragged: local crops without post_qformer");
-        TRY(resampler_validate(*post));
+        TRY(adapter_validate_post(mlp, attn, *post, &g));
         q = (*post)->n_query;
-        g = 0;
-        while (g * g < q) ++g;
-        SLIME_REQUIRE(g * g == q, "adapter: post_qformer query count %d is not a square grid", q);
     } else {
         *post = nullptr;
     }
@@ -688,7 +705,6 @@ static int ragged_layout(const slime_resampler_desc* attn, const slime_resampler
 static RaggedPlan ragged_plan(const slime_mlp_desc* m, const slime_resampler_desc* attn, const slime_resampler_desc* post, int n_images,
                               long total_local, int learnable_gated) {
     RaggedPlan p{};
-    p.total_local = total_local;
     p.a = adapter_plan_total(m, attn, post, n_images, total_local, learnable_gated);
     p.gtab = p.a.total;                                          // 256-B aligned
     p.ltab = p.gtab + align_up((size_t)n_images * sizeof(int), 256);
@@ -712,80 +728,19 @@ extern "C" int slime_adapter_forward_ragged(const slime_mlp_desc* mlp, const sli
                                             int learnable_gated, const slime_resampler_desc* post, const void* feats, int n_images,
                                             const int* nw, const int* nh, int merge, void* out, int out_dtype,
                                             const long long* out_row0, long out_rows, void* ws, size_t ws_bytes, void* stream) {
-    TRY(mlp_validate(mlp));
-    TRY(resampler_validate(attn));
-    SLIME_REQUIRE(feats && out, "adapter_ragged: bad input");
-    SLIME_REQUIRE(attn->dim == mlp->in_dim && attn->n_query == attn->n_kv, "adapter: attn must map the token grid onto itself");
-    SLIME_REQUIRE(learnable_gated >= 0 || w_gate, "adapter: missing w_gate");
-    SLIME_REQUIRE(learnable_gated <= 1, "adapter: expert index %d", learnable_gated);
-    SLIME_REQUIRE(attn->dtype == mlp->dtype, "adapter: mixed operand dtypes");
-    const int P = attn->n_kv, D = mlp->in_dim, H = mlp->hidden, dt = mlp->dtype;
-    SLIME_REQUIRE(out_dtype == SLIME_F32 || out_dtype == dt, "adapter_ragged: out_dtype %d is neither fp32 nor the operand type %d (a 16-bit "
-                  "output type other than the operand type is not stored through the row map: use the per-module path)", out_dtype, dt);
+    TRY(adapter_validate(mlp, attn, w_gate, learnable_gated, feats && out, "adapter_ragged"));
+    SLIME_REQUIRE(out_dtype == SLIME_F32 || out_dtype == mlp->dtype, "adapter_ragged: out_dtype %d is neither fp32 nor the operand type %d (a 16-bit "
+                  "output type other than the operand type is not stored through the row map: use the per-module path)", out_dtype, mlp->dtype);
     RaggedLayout L;
-    TRY(ragged_layout(attn, &post, n_images, nw, nh, merge, out_row0, out_rows, &L));
-    if (post)
-        SLIME_REQUIRE(post->dim == mlp->in_dim && post->n_kv == attn->n_kv && post->dtype == mlp->dtype, "adapter: post_qformer does not match the tower grid");
-    const long total_local = L.lrow0[n_images] / L.q;
-    const RaggedPlan rp = ragged_plan(mlp, attn, post, n_images, total_local, learnable_gated);
-    const AdapterPlan& p = rp.a;
-    if (!ws || ws_bytes < rp.total || ((uintptr_t)ws % 256) != 0) {
-        slime_set_error("adapter_ragged: workspace %zu B (need %zu, 256-B aligned)", ws_bytes, rp.total);
-        return SLIME_EWORKSPACE;
-    }
+    TRY(ragged_layout(mlp, attn, &post, n_images, nw, nh, merge, out_row0, out_rows, &L));
+    const RaggedPlan rp = ragged_plan(mlp, attn, post, n_images, L.lrow0[n_images] / L.q, learnable_gated);
+    TRY(ws_check("adapter_ragged", ws, ws_bytes, rp.total));
     char* w = (char*)ws;
-    float* xg32 = (float*)(w + p.xg32);
-    char* stack = w + p.stack;
-    int* rmap = (int*)(w + p.rmap);
+    int* rmap = (int*)(w + rp.a.rmap);
     int* gtab = (int*)(w + rp.gtab);
     int* ltab = (int*)(w + rp.ltab);
-
-    // stacked MLP input: [x_global | attn(x_global) | post_qformer(x_local)] (segments that are not needed are dropped)
-    size_t row = 0;
-    long seg_x = -1, seg_attn = -1, seg_local = -1;
-    if (learnable_gated != 1) { seg_x = (long)row; row += p.rows_g; }
-    if (learnable_gated != 0) { seg_attn = (long)row; row += p.rows_g; }
-    if (post) { seg_local = (long)row; row += p.rows_l; }
-
     // the device tables: projection[2]'s row map and the source crops of the global / local segments
     TRY(adapter_ragged_plan_launch(L, rmap, gtab, ltab, stream));
-    // global crops: fp32 copy for the resampler's LayerNorm and the gate logits, T copy straight into the stack
-    TRY(select_crops_indexed_launch(feats, dt, P, D, gtab, n_images, xg32, seg_x >= 0 ? stack + (size_t)seg_x * D * 2 : nullptr, stream));
-    if (seg_attn >= 0)
-        TRY(slime_resampler_forward(attn, xg32, D, n_images, nullptr, stack + (size_t)seg_attn * D * 2, w + p.res,
-                                    res_plan(attn, n_images).total, stream));
-    if (post) {
-        // local crops: post_qformer's first LayerNorm reads them straight from the tower's T features, through the crop table
-        const ResCrops rc{feats, 0, 0, 0, 0, ltab};
-        TRY(resampler_run(post, nullptr, 0, &rc, (int)total_local, nullptr, stack + (size_t)seg_local * D * 2, w + p.res,
-                          res_plan(post, (int)total_local).total, stream));
-    }
-    // projection MLP over the stack, as in slime_adapter_forward; projection[2] stores every row through the row map
-    const MlpPlan mp = mlp_plan(mlp, (int)p.rows_all);
-    char* mid = w + p.mlp + mp.mid;
-    auto projection2 = [&](const void* A, int rows) -> int {     // rows = [global | local] rows of the hidden activations
-        slime_gemm_args a{};
-        a.A = A; a.lda = H; a.B = mlp->w2; a.B_frag = mlp->w2_frag; a.bias = mlp->b2; a.M = rows; a.N = H; a.K = H; a.dtype = dt;
-        a.C = out; a.ldc = H; a.row_map = rmap; a.epilogue = out_dtype == SLIME_F32 ? SLIME_EPI_BIAS_F32 : SLIME_EPI_BIAS_T;
-        return slime_gemm_ex(&a, stream);
-    };
-    if (learnable_gated < 0) {
-        char* mixed = mid + (size_t)seg_attn * H * 2;
-        if (mix_in_gemm(mlp)) {
-            float* gates = (float*)(w + p.gates);
-            TRY(slime_gate_weights(xg32, D, w_gate, gates, (int)p.rows_g, stream));
-            TRY(gemm_mix(stack + (size_t)seg_x * D * 2, stack + (size_t)seg_attn * D * 2, gates, mlp, mixed, (int)p.rows_g, stream));
-            if (post)
-                TRY(gemm_w(stack + (size_t)seg_local * D * 2, D, mlp->w1, mlp->w1_frag, mlp->b1, mid + (size_t)seg_local * H * 2, H,
-                           (int)p.rows_l, H, D, dt, SLIME_EPI_BIAS_GELU_T, stream));
-        } else {
-            TRY(gemm_w(stack, D, mlp->w1, mlp->w1_frag, mlp->b1, mid, H, (int)p.rows_all, H, D, dt, SLIME_EPI_BIAS_GELU_T, stream));
-            TRY(slime_gate_premix(xg32, D, w_gate, mid + (size_t)seg_x * H * 2, mixed, mixed, dt, (int)p.rows_g, H, stream));
-        }
-        TRY(projection2(mixed, (int)(p.rows_g + p.rows_l)));
-    } else {
-        TRY(gemm_w(stack, D, mlp->w1, mlp->w1_frag, mlp->b1, mid, H, (int)p.rows_all, H, D, dt, SLIME_EPI_BIAS_GELU_T, stream));
-        TRY(projection2(mid, (int)p.rows_all));
-    }
-    return SLIME_OK;
+    const ResCrops glob{feats, 0, 0, 0, 0, gtab}, local{feats, 0, 0, 0, 0, ltab};
+    return adapter_run(mlp, attn, w_gate, post, rp.a, w, glob, local, nullptr, rmap, out, out_dtype, stream);
 }

@@ -470,6 +470,13 @@ extern "C" int slime_gather_rows_split(const void* hi, const void* lo, int dtype
     return SLIME_OK;
 }
 
+// Row rr = (crop k, qy, qx) of an image's local crops (g x g rows each, nw crops per grid row) -> its position in the merged raster
+__device__ __forceinline__ long merged_raster_row(long rr, int g, int nw) {
+    const int qx = (int)(rr % g), qy = (int)((rr / g) % g), k = (int)(rr / ((long)g * g));
+    const int gx = k % nw, gy = k / nw;
+    return ((long)(gy * g + qy) * nw + gx) * g + qx;
+}
+
 __global__ void __launch_bounds__(256) merge_rows_kernel(const float* in, long in_image_stride, void* out, int out_dtype,
                                                          long out_image_stride, long dst_row0, int nw, int nh, int g,
                                                          int C, int merge) {
@@ -477,12 +484,7 @@ __global__ void __launch_bounds__(256) merge_rows_kernel(const float* in, long i
     const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);       // input row of this image: (crop k, qy, qx)
     const long total = (long)nw * nh * g * g;
     if (r >= total) return;
-    long dst = r;
-    if (merge) {
-        const int qx = (int)(r % g), qy = (int)((r / g) % g), k = (int)(r / ((long)g * g));
-        const int gx = k % nw, gy = k / nw;
-        dst = ((long)(gy * g + qy) * nw + gx) * g + qx;
-    }
+    const long dst = merge ? merged_raster_row(r, g, nw) : r;
     const float* src = in + ((size_t)blockIdx.y * in_image_stride + (size_t)r) * C;
     const size_t drow = (size_t)blockIdx.y * out_image_stride + dst_row0 + dst;
     if (out_dtype == SLIME_F16) store_row_cast<F16>(src, out, drow, C, out_dtype, lane);
@@ -512,13 +514,7 @@ __global__ void __launch_bounds__(256) adapter_row_map_kernel(int* map, long row
         dst = (r / P) * out_image_stride + r % P;
     } else {
         const long q = r - rows_g, b = q / per_image_local, rr = q % per_image_local;
-        long d = rr;
-        if (merge) {
-            const int qx = (int)(rr % g), qy = (int)((rr / g) % g), k = (int)(rr / ((long)g * g));
-            const int gx = k % nw, gy = k / nw;
-            d = ((long)(gy * g + qy) * nw + gx) * g + qx;
-        }
-        dst = b * out_image_stride + P + d;
+        dst = b * out_image_stride + P + (merge ? merged_raster_row(rr, g, nw) : rr);
     }
     map[r] = (int)dst;
 }
@@ -537,7 +533,7 @@ int adapter_row_map_launch(int* map, long rows_g, int P, long rows_l, long per_i
 // Plan of the RAGGED fused adapter (slime_adapter_forward_ragged): every image has its own crop count, grid and first token row
 // (RaggedLayout, by value).  One thread per entry of three int32 tables:
 //   row_map     [B*P + sum n_i*q]  adapter_row_map_kernel's arithmetic with image b's own nw / n / dst0
-//   glob_crops  [B]                index in feats of each image's global crop            (select_crops_indexed_kernel)
+//   glob_crops  [B]                index in feats of each image's global crop            (select_crops_kernel<T, CropTable>)
 //   local_crops [sum n_i]          index in feats of each local crop, in image order    (layernorm_indexed_kernel)
 // The image of a local row is found by a scan over the prefix array in the kernel arguments (at most 64 steps; the index is per lane, so
 // the reads are vector loads from the argument segment -- no scratch, no table in memory).
@@ -555,13 +551,7 @@ __global__ void __launch_bounds__(256) adapter_ragged_plan_kernel(RaggedLayout L
         int b = 0;
         while (b < B - 1 && e >= L.lrow0[b + 1]) ++b;
         const long rr = e - L.lrow0[b];
-        long d = rr;
-        if (L.merge) {
-            const int g = L.g, nw = L.nw[b];
-            const int qx = (int)(rr % g), qy = (int)((rr / g) % g), k = (int)(rr / ((long)g * g));
-            const int gx = k % nw, gy = k / nw;
-            d = ((long)(gy * g + qy) * nw + gx) * g + qx;
-        }
+        const long d = L.merge ? merged_raster_row(rr, L.g, L.nw[b]) : rr;
         row_map[rows_g + e] = L.dst0[b] + L.P + (int)d;
         return;
     }
@@ -597,14 +587,17 @@ extern "C" int slime_merge_rows(const float* in, void* out, int out_dtype, long 
 // crops: output crop j = image (j / per_image) * period + first + j % per_image.  One wave per row,
 // 16 B per lane per step.
 // ------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void __launch_bounds__(256) select_crops_kernel(const char* feats, int P, int C, int period, int first,
-                                                           int per_image, long rows, float* out_f32, char* out_t) {
+// the source crop of output crop j: the uniform window arithmetic, or a DEVICE table (ragged fused adapter)
+struct CropWindow { int period, first, per_image; __device__ long operator()(long j) const { return (j / per_image) * period + first + j % per_image; } };
+struct CropTable { const int* table; __device__ long operator()(long j) const { return table[j]; } };
+
+template <typename T, typename Src>
+__global__ void __launch_bounds__(256) select_crops_kernel(const char* feats, int P, int C, Src crop_of, long rows, float* out_f32, char* out_t) {
     const int lane = threadIdx.x & 63;
     const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
     const long j = r / P, i = r % P;
-    const long crop = (j / per_image) * period + first + j % per_image;
+    const long crop = crop_of(j);
     const char* src = feats + ((size_t)crop * P + i) * C * 2;
     for (int c = lane * 8; c < C; c += 512) {
         const u32x4 v = *reinterpret_cast<const u32x4*>(src + (size_t)c * 2);
@@ -615,6 +608,13 @@ __global__ void __launch_bounds__(256) select_crops_kernel(const char* feats, in
             *reinterpret_cast<float4*>(d + 4) = make_float4(T::lo(v[2]), T::hi(v[2]), T::lo(v[3]), T::hi(v[3]));
         }
     }
+}
+
+template <typename Src>
+static void select_crops_launch(const void* feats, int dtype, int P, int C, Src crop_of, long rows, float* out_f32, void* out_t, void* stream) {
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (dtype == SLIME_F16) hipLaunchKernelGGL((select_crops_kernel<F16, Src>), grid, dim3(256), 0, (hipStream_t)stream, (const char*)feats, P, C, crop_of, rows, out_f32, (char*)out_t);
+    else hipLaunchKernelGGL((select_crops_kernel<BF16, Src>), grid, dim3(256), 0, (hipStream_t)stream, (const char*)feats, P, C, crop_of, rows, out_f32, (char*)out_t);
 }
 
 extern "C" int slime_select_crops(const void* feats, int dtype, int P, int C, int period, int first, int per_image,
@@ -622,44 +622,17 @@ extern "C" int slime_select_crops(const void* feats, int dtype, int P, int C, in
     SLIME_REQUIRE(feats && (out_f32 || out_t) && P > 0 && C % 8 == 0 && per_image > 0 && images > 0, "select_crops: bad input");
     SLIME_REQUIRE(first >= 0 && first + per_image <= period, "select_crops: window outside the image's crops");
     SLIME_REQUIRE(dtype == SLIME_BF16 || dtype == SLIME_F16, "select_crops: features must be BF16 or F16");
-    const long rows = (long)images * per_image * P;
-    dim3 grid((unsigned)((rows + 3) / 4));
-    if (dtype == SLIME_F16) hipLaunchKernelGGL(select_crops_kernel<F16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)feats, P, C, period, first, per_image, rows, out_f32, (char*)out_t);
-    else hipLaunchKernelGGL(select_crops_kernel<BF16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)feats, P, C, period, first, per_image, rows, out_f32, (char*)out_t);
+    select_crops_launch(feats, dtype, P, C, CropWindow{period, first, per_image}, (long)images * per_image * P, out_f32, out_t, stream);
     SLIME_CHECK_LAUNCH("select_crops");
     return SLIME_OK;
 }
 
-// The same with the source crop of output crop j read from a DEVICE table (ragged fused adapter): crop = table[j].
-template <typename T>
-__global__ void __launch_bounds__(256) select_crops_indexed_kernel(const char* feats, int P, int C, const int* table, long rows,
-                                                                   float* out_f32, char* out_t) {
-    const int lane = threadIdx.x & 63;
-    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;
-    const long j = r / P, i = r % P;
-    const long crop = table[j];
-    const char* src = feats + ((size_t)crop * P + i) * C * 2;
-    for (int c = lane * 8; c < C; c += 512) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(src + (size_t)c * 2);
-        if (out_t) *reinterpret_cast<u32x4*>(out_t + ((size_t)r * C + c) * 2) = v;
-        if (out_f32) {
-            float* d = out_f32 + (size_t)r * C + c;
-            *reinterpret_cast<float4*>(d) = make_float4(T::lo(v[0]), T::hi(v[0]), T::lo(v[1]), T::hi(v[1]));
-            *reinterpret_cast<float4*>(d + 4) = make_float4(T::lo(v[2]), T::hi(v[2]), T::lo(v[3]), T::hi(v[3]));
-        }
-    }
-}
-
-// internal (not part of the C ABI)
+// internal (not part of the C ABI): the same with crop = table[j]
 int select_crops_indexed_launch(const void* feats, int dtype, int P, int C, const int* table, int n_crops, float* out_f32, void* out_t,
                                 void* stream) {
     SLIME_REQUIRE(feats && table && (out_f32 || out_t) && P > 0 && C % 8 == 0 && n_crops > 0, "select_crops_indexed: bad input");
     SLIME_REQUIRE(dtype == SLIME_BF16 || dtype == SLIME_F16, "select_crops_indexed: features must be BF16 or F16");
-    const long rows = (long)n_crops * P;
-    dim3 grid((unsigned)((rows + 3) / 4));
-    if (dtype == SLIME_F16) hipLaunchKernelGGL(select_crops_indexed_kernel<F16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)feats, P, C, table, rows, out_f32, (char*)out_t);
-    else hipLaunchKernelGGL(select_crops_indexed_kernel<BF16>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)feats, P, C, table, rows, out_f32, (char*)out_t);
+    select_crops_launch(feats, dtype, P, C, CropTable{table}, (long)n_crops * P, out_f32, out_t, stream);
     SLIME_CHECK_LAUNCH("select_crops_indexed");
     return SLIME_OK;
 }

@@ -13,7 +13,7 @@ import os
 import threading
 import weakref
 from dataclasses import dataclass, field
-from typing import Dict, List, NamedTuple, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -59,6 +59,12 @@ class Workspace:
         if self.buf is None or self.buf.numel() < nbytes or self.buf.device != torch.device(device):
             self.buf = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=device)
         return self.buf
+
+    def aligned(self, nbytes: int, device) -> Tuple[int, int]:
+        """``get``, as what a C entry takes: (the 256-B aligned base address, the bytes available behind it)."""
+        buf = self.get(nbytes, device)
+        base = (buf.data_ptr() + 255) // 256 * 256
+        return base, buf.numel() - (base - buf.data_ptr())
 
 
 # ------------------------------------------------------------------------------------------------
@@ -123,9 +129,7 @@ def _launch_gemm(g: "_lib.GemmArgs", splits: int, device, ws: Optional[torch.Ten
         _lib.check(lib.slime_gemm_ex(C.byref(g), _stream()), "slime_gemm_ex")
         return
     if ws is None:
-        buf = _ksplit_ws.get(lib.slime_gemm_ksplit_workspace_bytes(g.M, g.N, splits), device)
-        base = (buf.data_ptr() + 255) // 256 * 256
-        nbytes = buf.numel() - (base - buf.data_ptr())
+        base, nbytes = _ksplit_ws.aligned(lib.slime_gemm_ksplit_workspace_bytes(g.M, g.N, splits), device)
     else:
         base, nbytes = ws.data_ptr(), ws.numel() * ws.element_size()
     _lib.check(lib.slime_gemm_ksplit(C.byref(g), int(splits), base, nbytes, _stream()), "slime_gemm_ksplit")
@@ -424,22 +428,20 @@ def tower_forward(pt: PackedTower, pixels: torch.Tensor, out_dtype: Optional[tor
             raise ValueError("tower_forward: the timing probe goes with k_split=None (slime_vit_forward_ex)")
         ks = _lib.VitKsplit(*(int(v) for v in k_split))
         need = lib.slime_vit_ksplit_workspace_bytes(C.byref(pt.desc), n, C.byref(ks))
-        ws = pt.ws.get(need, pixels.device)
-        base = (ws.data_ptr() + 255) // 256 * 256
+        base, avail = pt.ws.aligned(need, pixels.device)
         _lib.check(lib.slime_vit_forward_ksplit(C.byref(pt.desc), pixels.data_ptr(), dtype_code(pixels.dtype), n, out.data_ptr(),
                                                 dtype_code(out_dtype), int(keep_cls), _ptr(hidden), C.byref(ks), base,
-                                                ws.numel() - (base - ws.data_ptr()), _stream()), "slime_vit_forward_ksplit")
+                                                avail, _stream()), "slime_vit_forward_ksplit")
         return (out, hidden) if want_hidden else out
     need = lib.slime_vit_workspace_bytes(C.byref(pt.desc), n)
-    ws = pt.ws.get(need, pixels.device)
-    base = (ws.data_ptr() + 255) // 256 * 256
+    base, avail = pt.ws.aligned(need, pixels.device)
     probe = None
     if pt.probe is not None:
         layer, kernel, e0, e1 = pt.probe
         probe = C.byref(_lib.Probe(int(layer), int(kernel), e0.cuda_event, e1.cuda_event))
     _lib.check(lib.slime_vit_forward_ex(C.byref(pt.desc), pixels.data_ptr(), dtype_code(pixels.dtype), n, out.data_ptr(),
                                         dtype_code(out_dtype), int(keep_cls), _ptr(hidden), base,
-                                        ws.numel() - (base - ws.data_ptr()), _stream(), probe), "slime_vit_forward")
+                                        avail, _stream(), probe), "slime_vit_forward")
     return (out, hidden) if want_hidden else out
 
 
@@ -456,10 +458,9 @@ def tower_hidden_states(pt: PackedTower, pixels: torch.Tensor) -> torch.Tensor:
     n = pixels.shape[0]
     states = torch.empty((pt.layers_run + 1, n, cfg.seq_len, cfg.hidden_size), dtype=torch.float32, device=pixels.device)
     need = lib.slime_vit_workspace_bytes(C.byref(pt.desc), n)
-    ws = pt.ws.get(need, pixels.device)
-    base = (ws.data_ptr() + 255) // 256 * 256
+    base, avail = pt.ws.aligned(need, pixels.device)
     _lib.check(lib.slime_vit_forward_states(C.byref(pt.desc), pixels.data_ptr(), dtype_code(pixels.dtype), n, states.data_ptr(), base,
-                                            ws.numel() - (base - ws.data_ptr()), _stream()), "slime_vit_forward_states")
+                                            avail, _stream()), "slime_vit_forward_states")
     return states
 
 
@@ -553,10 +554,9 @@ def resampler_forward(pr: PackedResampler, x: torch.Tensor, want_t: bool = False
     out = torch.empty((n, pr.n_query, pr.dim), dtype=torch.float32, device=x.device)
     out_t = torch.empty((n, pr.n_query, pr.dim), dtype=pr.dtype, device=x.device) if want_t else None
     need = lib.slime_resampler_workspace_bytes(C.byref(pr.desc), n)
-    ws = pr.ws.get(need, x.device)
-    base = (ws.data_ptr() + 255) // 256 * 256
+    base, avail = pr.ws.aligned(need, x.device)
     _lib.check(lib.slime_resampler_forward(C.byref(pr.desc), x.data_ptr(), pr.dim, n, out.data_ptr(), _ptr(out_t), base,
-                                           ws.numel() - (base - ws.data_ptr()), _stream()), "slime_resampler_forward")
+                                           avail, _stream()), "slime_resampler_forward")
     return (out, out_t) if want_t else out
 
 
@@ -591,15 +591,14 @@ def mlp_forward(pm: PackedMlp, x: torch.Tensor) -> torch.Tensor:
     rows = x.shape[0]
     out = torch.empty((rows, pm.hidden), dtype=torch.float32, device=x.device)
     need = lib.slime_mlp_workspace_bytes(C.byref(pm.desc), rows)
-    ws = pm.ws.get(need, x.device)
-    base = (ws.data_ptr() + 255) // 256 * 256
+    base, avail = pm.ws.aligned(need, x.device)
     xf = x.data_ptr() if x.dtype == torch.float32 else None
     xt = x.data_ptr() if x.dtype == pm.dtype else None
     if xf is None and xt is None:
         x = x.float()
         xf = x.data_ptr()
     _lib.check(lib.slime_mlp_forward(C.byref(pm.desc), xf, xt, rows, out.data_ptr(), base,
-                                     ws.numel() - (base - ws.data_ptr()), _stream()), "slime_mlp_forward")
+                                     avail, _stream()), "slime_mlp_forward")
     return out
 
 
@@ -631,12 +630,22 @@ def gated_forward(pg: PackedGated, x: torch.Tensor, learnable_gated: int = -1) -
     assert Tn == pg.attn.n_kv and D == pg.mlp.in_dim
     out = torch.empty((n, Tn, pg.mlp.hidden), dtype=torch.float32, device=x.device)
     need = lib.slime_gated_workspace_bytes(C.byref(pg.mlp.desc), C.byref(pg.attn.desc), n)
-    ws = pg.ws.get(need, x.device)
-    base = (ws.data_ptr() + 255) // 256 * 256
+    base, avail = pg.ws.aligned(need, x.device)
     _lib.check(lib.slime_gated_forward(C.byref(pg.mlp.desc), C.byref(pg.attn.desc), pg.w_gate.data_ptr(),
                                        int(learnable_gated), x.data_ptr(), n, out.data_ptr(), base,
-                                       ws.numel() - (base - ws.data_ptr()), _stream()), "slime_gated_forward")
+                                       avail, _stream()), "slime_gated_forward")
     return out
+
+
+def _adapter_feats(pg: PackedGated, feats: torch.Tensor) -> torch.Tensor:
+    """Tower features as both fused adapter entries take them: on the GPU, in the operand dtype, contiguous."""
+    _require_cuda(feats, "feats")
+    return feats.to(pg.mlp.dtype).contiguous()
+
+
+def _post_desc(post: Optional["PackedResampler"], any_local):
+    """post_qformer's descriptor, or NULL for a batch without local crops."""
+    return C.byref(post.desc) if any_local else None
 
 
 def adapter_forward(pg: PackedGated, post: Optional["PackedResampler"], feats: torch.Tensor, n_images: int, n_local: int,
@@ -646,23 +655,18 @@ def adapter_forward(pg: PackedGated, post: Optional["PackedResampler"], feats: t
     tokens [n_images, 576 + n_local*g*g, H] (gated global rows, then the merged local rows).  ``out`` may be a
     wider [n_images, rows, H] buffer (extra rows per image are left untouched)."""
     lib = _lib.load()
-    _require_cuda(feats, "feats")
-    if feats.dtype != pg.mlp.dtype:
-        feats = feats.to(pg.mlp.dtype)
-    feats = feats.contiguous()
+    feats = _adapter_feats(pg, feats)
     assert feats.shape[0] == n_images * (1 + n_local) and feats.shape[1] == pg.attn.n_kv and feats.shape[2] == pg.mlp.in_dim
     rows = pg.attn.n_kv + (n_local * post.n_query if n_local else 0)
     if out is None:
         out = torch.empty((n_images, rows, pg.mlp.hidden), dtype=out_dtype or feats.dtype, device=feats.device)
     assert out.dim() == 3 and out.shape[0] == n_images and out.shape[1] >= rows and out.shape[2] == pg.mlp.hidden and out.is_contiguous()
-    pdesc = C.byref(post.desc) if n_local else None
+    pdesc = _post_desc(post, n_local)
     need = lib.slime_adapter_workspace_bytes(C.byref(pg.mlp.desc), C.byref(pg.attn.desc), pdesc, n_images, n_local)
-    ws = pg.ws.get(need, feats.device)
-    base = (ws.data_ptr() + 255) // 256 * 256
+    base, avail = pg.ws.aligned(need, feats.device)
     _lib.check(lib.slime_adapter_forward(C.byref(pg.mlp.desc), C.byref(pg.attn.desc), pg.w_gate.data_ptr(), int(learnable_gated),
                                          pdesc, feats.data_ptr(), n_images, n_local, nw, nh, int(merge), out.data_ptr(),
-                                         dtype_code(out.dtype), out.shape[1], base, ws.numel() - (base - ws.data_ptr()),
-                                         _stream()), "slime_adapter_forward")
+                                         dtype_code(out.dtype), out.shape[1], base, avail, _stream()), "slime_adapter_forward")
     return out
 
 
@@ -715,10 +719,7 @@ def adapter_forward_ragged(pg: PackedGated, post: Optional["PackedResampler"], f
     n_i*g*g)`` -- gated global rows, then its local rows in raster order of its own grid.  ``out`` may be a larger flat [rows, H]
     buffer (fp32 or T) with ``out_row0`` chosen by the caller; rows no image owns are left untouched."""
     lib = _lib.load()
-    _require_cuda(feats, "feats")
-    if feats.dtype != pg.mlp.dtype:
-        feats = feats.to(pg.mlp.dtype)
-    feats = feats.contiguous()
+    feats = _adapter_feats(pg, feats)
     grids = [(int(nw), int(nh)) for nw, nh in grids]
     B, n_crops = len(grids), sum(1 + nw * nh for nw, nh in grids)
     if feats.dim() != 3 or feats.shape[0] != n_crops or feats.shape[1] != pg.attn.n_kv or feats.shape[2] != pg.mlp.in_dim:
@@ -735,14 +736,12 @@ def adapter_forward_ragged(pg: PackedGated, post: Optional["PackedResampler"], f
     nw_a = (C.c_int * max(B, 1))(*[g[0] for g in grids])
     nh_a = (C.c_int * max(B, 1))(*[g[1] for g in grids])
     r0_a = (C.c_longlong * max(B, 1))(*row0) if out_row0 is not None else None
-    pdesc = C.byref(post.desc) if any_local else None
+    pdesc = _post_desc(post, any_local)
     need = lib.slime_adapter_ragged_workspace_bytes(C.byref(pg.mlp.desc), C.byref(pg.attn.desc), pdesc, B, nw_a, nh_a)
-    ws = pg.ws.get(max(need, 256), feats.device)
-    base = (ws.data_ptr() + 255) // 256 * 256
+    base, avail = pg.ws.aligned(max(need, 256), feats.device)
     _lib.check(lib.slime_adapter_forward_ragged(C.byref(pg.mlp.desc), C.byref(pg.attn.desc), pg.w_gate.data_ptr(), int(learnable_gated),
                                                 pdesc, feats.data_ptr(), B, nw_a, nh_a, int(merge), out.data_ptr(), dtype_code(out.dtype),
-                                                r0_a, out.shape[0], base, ws.numel() - (base - ws.data_ptr()), _stream()),
-               "slime_adapter_forward_ragged")
+                                                r0_a, out.shape[0], base, avail, _stream()), "slime_adapter_forward_ragged")
     return out, row0
 
 
@@ -1201,13 +1200,12 @@ def router_attention_scores(pra: PackedRouterAttention, tokens: torch.Tensor, ro
     idx = torch.cat([torch.from_numpy(tok_idx), torch.from_numpy(key_idx)]).to(dev, non_blocking=True)   # one upload
     sum_T, sum_L = int(tok_idx.size), int(key_idx.size)
     need = lib.slime_router_attn_workspace_bytes(C.byref(pra.desc), sum_T, sum_L)
-    ws = pra.ws.get(need, dev)
-    base = (ws.data_ptr() + 255) // 256 * 256
+    base, avail = pra.ws.aligned(need, dev)
     nr = (C.c_int * B)(*[int(n) for n in n_rows])
     nk = (C.c_int * B)(*n_keys)
     _lib.check(lib.slime_router_attn_scores(C.byref(pra.desc), tokens.data_ptr(), tokens.shape[0], idx.data_ptr(), nr, txt.data_ptr(),
                                             B * L, idx.data_ptr() + 8 * sum_T, nk, B, T_max, float(temp), scores.data_ptr(), base,
-                                            ws.numel() - (base - ws.data_ptr()), _stream()), "slime_router_attn_scores")
+                                            avail, _stream()), "slime_router_attn_scores")
     return scores
 
 
@@ -1487,11 +1485,9 @@ def llama_attention_forward_resid(pa: PackedLlamaAttention, hidden: torch.Tensor
         out = torch.empty((B, S, D), dtype=pa.dtype, device=x.device)
     assert out.is_contiguous() and out.dtype == pa.dtype and out.data_ptr() != x.data_ptr()
     need = lib.slime_llama_attn_workspace_bytes(C.byref(pa.desc), B, S)
-    ws = pa.ws.get(need, x.device)
-    base = (ws.data_ptr() + 255) // 256 * 256
+    base, avail = pa.ws.aligned(need, x.device)
     _lib.check(lib.slime_llama_attn_forward_resid(C.byref(pa.desc), x.data_ptr(), pos.data_ptr(), _ptr(start), _ptr(length), B, S,
-                                                  r.data_ptr(), out.data_ptr(), base, ws.numel() - (base - ws.data_ptr()), _stream()),
-               "slime_llama_attn_forward_resid")
+                                                  r.data_ptr(), out.data_ptr(), base, avail, _stream()), "slime_llama_attn_forward_resid")
     return out
 
 
@@ -1509,9 +1505,7 @@ def llama_attention_forward(pa: PackedLlamaAttention, hidden: torch.Tensor, posi
     kernel_out = torch.float32 if out_dtype == torch.float32 else pa.dtype
     out = torch.empty((B, S, D), dtype=kernel_out, device=x.device)
     need = lib.slime_llama_attn_workspace_bytes(C.byref(pa.desc), B, S)
-    ws = pa.ws.get(need, x.device)
-    base = (ws.data_ptr() + 255) // 256 * 256
+    base, avail = pa.ws.aligned(need, x.device)
     _lib.check(lib.slime_llama_attn_forward(C.byref(pa.desc), x.data_ptr(), pos.data_ptr(), _ptr(start), _ptr(length), B, S,
-                                            out.data_ptr(), dtype_code(kernel_out), base, ws.numel() - (base - ws.data_ptr()),
-                                            _stream()), "slime_llama_attn_forward")
+                                            out.data_ptr(), dtype_code(kernel_out), base, avail, _stream()), "slime_llama_attn_forward")
     return out if out.dtype == out_dtype else out.to(out_dtype)

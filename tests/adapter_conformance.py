@@ -464,9 +464,10 @@ def replay_gated(be, pg, x, n: int, learnable_gated: int):
 
 
 def _adapter_core(be, pg, post, feats, gi, li, learnable_gated, out, direct, rmap, merge_args, broken):
-    """What slime_adapter_forward and slime_adapter_forward_ragged share: gi / li = feats indices of the global / local crops,
-    rmap = projection[2]'s row map (direct store) or merge_args = (out_image_stride, n_local, nw, nh, g, merge, local row0) for the
-    fp32 rows + slime_merge_rows_batched path.  ``out`` [rows, H] is written in place."""
+    """What slime_adapter_forward and slime_adapter_forward_ragged share, api.hip's ``adapter_run`` (the both-experts block is its
+    ``both_experts_hidden``): gi / li = feats indices of the global / local crops (adapter_run's two crop sources), rmap =
+    projection[2]'s row map (direct store) or merge_args = (out_image_stride, n_local, nw, nh, g, merge, local row0) for the fp32 rows +
+    slime_merge_rows_batched path, which the uniform entry runs behind adapter_run.  ``out`` [rows, H] is written in place."""
     m, T = pg.mlp, pg.mlp.tensors
     P, D, H = pg.attn.n_kv, m.in_dim, m.hidden
     n_images = len(gi)
