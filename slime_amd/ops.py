@@ -311,49 +311,55 @@ def layers_for_select(cfg: VisionConfig, select_layer: int) -> int:
     return idx
 
 
-def pack_tower(state_dict: Dict[str, torch.Tensor], cfg: VisionConfig, dtype: torch.dtype, device,
-               select_layer: int = -2) -> PackedTower:
-    """HF CLIPVisionModel state dict (either key generation) -> device tensors in the kernels' layout."""
-    if dtype not in (torch.bfloat16, torch.float16):
+def fold_ln(Wm, bm, gamma, beta, row_scale=None, dtype: Optional[torch.dtype] = None):
+    """LayerNorm folded into the Linear that consumes it (slime_gemm_ex): W' = T(W diag(gamma) rowscale), b' = (b + W beta) rowscale,
+    colsum = row sums of the ROUNDED W' (it must cancel the mean term of what the MFMA multiplies).  Host tensors: (W' T, b' fp32,
+    colsum fp32); dtype = None rounds nothing (all three float64)."""
+    W64 = Wm.detach().double().cpu()
+    Wp = W64 * gamma.detach().double().cpu()[None, :]
+    bp = bm.detach().double().cpu() + W64 @ beta.detach().double().cpu()
+    if row_scale is not None:
+        Wp, bp = Wp * row_scale[:, None], bp * row_scale
+    if dtype is None:
+        return Wp, bp, Wp.sum(1)
+    Wt = Wp.float().to(dtype)
+    return Wt, bp.float(), Wt.double().sum(1).float()
+
+
+def tower_host_tensors(state_dict: Dict[str, torch.Tensor], cfg: VisionConfig, dtype: Optional[torch.dtype],
+                       select_layer: int = -2) -> Dict[str, torch.Tensor]:
+    """The pack-time algebra of ``pack_tower`` on the host (no device work; CPU tensors out): the conv weight as a zero-padded
+    [D, kpad] matrix, and per layer (stacked along dim 0, ``layers_for_select`` layers) [q; k; v] with LayerNorm1 and the q scale
+    dh^-0.5 log2(e) folded in (``fold_ln``), fc1 with LayerNorm2 folded in, out_proj and fc2 as they are.  Matrices in ``dtype``,
+    everything else fp32; ``dtype=None``: nothing is rounded, every tensor float64."""
+    if dtype not in (None, torch.bfloat16, torch.float16):
         raise ValueError("tower compute dtype must be bf16 or fp16 (MFMA operand type); fp32 I/O is supported")
     sd = strip_tower_prefix(state_dict)
-    D, Fi, L = cfg.hidden_size, cfg.intermediate_size, layers_for_select(cfg, select_layer)
+    D, L = cfg.hidden_size, layers_for_select(cfg, select_layer)
     P2 = 3 * cfg.patch_size * cfg.patch_size
     kpad = (P2 + 63) // 64 * 64
     scale = cfg.head_dim ** -0.5 * LOG2E                     # logits in log2 units (slime_attention contract)
 
     def f32(t):
-        return t.detach().to(device=device, dtype=torch.float32).contiguous()
+        t = t.detach().cpu()
+        return (t.double() if dtype is None else t.float()).contiguous()
 
     def tt(t):
-        return t.detach().to(device=device, dtype=torch.float32).to(dtype).contiguous()
+        t = t.detach().cpu()
+        return (t.double() if dtype is None else t.float().to(dtype)).contiguous()
 
     pw = torch.zeros((D, kpad), dtype=torch.float32)
-    pw[:, :P2] = sd["embeddings.patch_embedding.weight"].detach().float().reshape(D, P2)
+    pw[:, :P2] = sd["embeddings.patch_embedding.weight"].detach().float().cpu().reshape(D, P2)
     T: Dict[str, torch.Tensor] = {
         "patch_w": tt(pw), "cls": f32(sd["embeddings.class_embedding"]),
         "pos": f32(sd["embeddings.position_embedding.weight"]),
         "pre_ln_w": f32(sd["pre_layrnorm.weight"]), "pre_ln_b": f32(sd["pre_layrnorm.bias"]),
     }
-
-    def stack(fmt, conv, n=L):
-        if n == 0:
-            return None
-        return torch.stack([conv(sd[fmt.format(i)]) for i in range(n)]).contiguous()
-
     if L > 0:
         p = "encoder.layers.{}."
 
-        def fold_ln(Wm, bm, gamma, beta, row_scale=None):
-            """LayerNorm folded into the Linear that consumes it (slime_gemm_ex): W' = W diag(gamma) rounded to T,
-            b' = b + W beta, colsum = row sums of the ROUNDED W' (it must cancel the mean term of what the MFMA multiplies)."""
-            W64 = Wm.detach().double().cpu()
-            Wp = W64 * gamma.detach().double().cpu()[None, :]
-            bp = bm.detach().double().cpu() + W64 @ beta.detach().double().cpu()
-            if row_scale is not None:
-                Wp, bp = Wp * row_scale[:, None], bp * row_scale
-            Wt = Wp.float().to(dtype)
-            return Wt, bp.float(), Wt.double().sum(1).float()
+        def stack(fmt, conv):
+            return torch.stack([conv(sd[fmt.format(i)]) for i in range(L)]).contiguous()
 
         rs = torch.ones(3 * D, dtype=torch.float64)
         rs[:D] = scale                                         # q rows carry dh^-0.5 * log2 e (slime_attention contract)
@@ -363,18 +369,32 @@ def pack_tower(state_dict: Dict[str, torch.Tensor], cfg: VisionConfig, dtype: to
             a = q + "self_attn."
             Wm = torch.cat([sd[a + "q_proj.weight"].float(), sd[a + "k_proj.weight"].float(), sd[a + "v_proj.weight"].float()], 0)
             bm = torch.cat([sd[a + "q_proj.bias"].float(), sd[a + "k_proj.bias"].float(), sd[a + "v_proj.bias"].float()], 0)
-            Wt, bp, cs = fold_ln(Wm, bm, sd[q + "layer_norm1.weight"], sd[q + "layer_norm1.bias"], rs)
+            Wt, bp, cs = fold_ln(Wm, bm, sd[q + "layer_norm1.weight"], sd[q + "layer_norm1.bias"], rs, dtype)
             wq.append(Wt); bq.append(bp); cq.append(cs)
-            Wt, bp, cs = fold_ln(sd[q + "mlp.fc1.weight"], sd[q + "mlp.fc1.bias"], sd[q + "layer_norm2.weight"], sd[q + "layer_norm2.bias"])
+            Wt, bp, cs = fold_ln(sd[q + "mlp.fc1.weight"], sd[q + "mlp.fc1.bias"], sd[q + "layer_norm2.weight"], sd[q + "layer_norm2.bias"],
+                                 None, dtype)
             w1.append(Wt); b1.append(bp); c1.append(cs)
 
-        def dev_stack(ts):
-            return torch.stack(ts).to(device).contiguous()
+        def host_stack(ts):
+            return torch.stack(ts).contiguous()
 
-        T["w_qkv"], T["b_qkv"], T["colsum_qkv"] = dev_stack(wq), dev_stack(bq), dev_stack(cq)
-        T["w_fc1"], T["b_fc1"], T["colsum_fc1"] = dev_stack(w1), dev_stack(b1), dev_stack(c1)
+        T["w_qkv"], T["b_qkv"], T["colsum_qkv"] = host_stack(wq), host_stack(bq), host_stack(cq)
+        T["w_fc1"], T["b_fc1"], T["colsum_fc1"] = host_stack(w1), host_stack(b1), host_stack(c1)
         T["w_o"], T["b_o"] = stack(p + "self_attn.out_proj.weight", tt), stack(p + "self_attn.out_proj.bias", f32)
         T["w_fc2"], T["b_fc2"] = stack(p + "mlp.fc2.weight", tt), stack(p + "mlp.fc2.bias", f32)
+    return T
+
+
+def pack_tower(state_dict: Dict[str, torch.Tensor], cfg: VisionConfig, dtype: torch.dtype, device,
+               select_layer: int = -2) -> PackedTower:
+    """HF CLIPVisionModel state dict (either key generation) -> device tensors in the kernels' layout (``tower_host_tensors`` on
+    ``device``, the four layer matrices and the conv weight also in MFMA-fragment order)."""
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("tower compute dtype must be bf16 or fp16 (MFMA operand type); fp32 I/O is supported")
+    D, Fi, L = cfg.hidden_size, cfg.intermediate_size, layers_for_select(cfg, select_layer)
+    kpad = (3 * cfg.patch_size * cfg.patch_size + 63) // 64 * 64
+    T: Dict[str, torch.Tensor] = {k: v.to(device).contiguous() for k, v in tower_host_tensors(state_dict, cfg, dtype, select_layer).items()}
+    if L > 0:
         # fragment-order images (the direct-B kernel loads them straight into registers, the LDS-staged kernels DMA from them);
         # the row-major tensors are dropped unless SLIME_KEEP_ROW_MAJOR=1
         pack_static(T, ("w_qkv", "w_o", "w_fc1", "w_fc2"))
