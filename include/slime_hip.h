@@ -82,9 +82,11 @@ int slime_gemm(const void* A, int lda, const void* B, const float* bias, void* C
  * the LayerNorm launches and the fp32 re-read of the residual stream from the tower:
  *   producer (epilogue SLIME_EPI_BIAS_RESID_F32_LN, the out_proj / fc2 GEMM that updates the residual stream C): also writes
  *     x16[M, ldx] = T(C) and stats_out[M, N/64, 2] = (sum, sum of squares) of the updated fp32 row over each 64-column group;
- *   consumer (ln_stats != NULL; epilogue BIAS_T or BIAS_QUICKGELU_T): A = x16 (un-normalised), B = W . diag(gamma) rounded to T,
- *     bias = b + W beta, ln_colsum[n] = sum_k B[n, k]; the epilogue evaluates rstd * (acc - mu * ln_colsum[n]) + bias[n] with
- *     mu / rstd = rsqrt(var + ln_eps) from the ln_groups partial sums of each row (K = the normalised width).
+ *   consumer (ln_stats != NULL; epilogue BIAS_T, BIAS_QUICKGELU_T or BIAS_GELU_T): A = x16 (un-normalised), B = W . diag(gamma)
+ *     rounded to T, bias = b + W beta, ln_colsum[n] = sum_k B[n, k]; the epilogue evaluates rstd * (acc - mu * ln_colsum[n]) + bias[n]
+ *     with mu / rstd = rsqrt(var + ln_eps) from the ln_groups partial sums of each row (K = the normalised width), then the
+ *     epilogue's activation on that pre-activation (BIAS_GELU_T: the erf form of the un-folded epilogue, for towers whose
+ *     hidden_act is 'gelu').
  * Identical to LayerNorm followed by the GEMM up to rounding (x is rounded to T before instead of after the normalisation). */
 typedef struct {
     const void* A; int lda; const void* B; const float* bias; void* C; int ldc;
@@ -131,7 +133,7 @@ int slime_gemm_b_frag_usable(int N, int K);
  *   reduce    one workgroup per output tile sums the planes in the fixed order ((p0 + p1) + p2) + ... in fp32  (SUMMATION ORDER)
  *             and applies the epilogue -- the same code, hence the same arithmetic, as slime_gemm_ex for BIAS_T, BIAS_QUICKGELU_T,
  *             BIAS_GELU_T, BIAS_F32, BIAS_RESID_F32, BIAS_RESID_F32_LN, BIAS_RESID_T, BIAS_RESID_SPLIT_LN (lo8, stats_out), the
- *             LayerNorm-fold consumer (ln_stats) and row_map.
+ *             LayerNorm-fold consumer (ln_stats with BIAS_T, BIAS_QUICKGELU_T or BIAS_GELU_T) and row_map.
  * A result element depends on (its row of A, B, K, splits) only: bit-identical for any M, any partition of the rows into calls or
  * rank shards, either tile the library picks and any of the three operand forms (B, B_frag, both); deterministic from run to run.
  * It is NOT bit-identical to the result of another `splits` (the fp32 sums associate differently); both lie within the same error
@@ -153,7 +155,7 @@ int slime_gemm_kernel_name(int M, int N, int K, int dtype, int epilogue, int has
  *   out_f32[r]  = y                            if out_f32
  *   out_t[r]    = T(y)                         if out_t
  *   out_t2[r]   = T(y + add[r % add_period])   if out_t2   (key position term, sampler.py:164)
- * D must be 128, 256 or 1024.  Replaces nn.LayerNorm (HF :370,379; sampler.py:106,158,168). */
+ * D must be 128, 256, 768 or 1024.  Replaces nn.LayerNorm (HF :370,379; sampler.py:106,158,168). */
 int slime_layernorm(const float* x, int ldx, int rows, int D, const float* w, const float* b, float eps,
                     int normalize, float* out_f32, void* out_t, void* out_t2, const float* add,
                     int add_period, int dtype, void* stream);
@@ -170,9 +172,10 @@ int slime_layernorm(const float* x, int ldx, int rows, int D, const float* w, co
  *   x16   T   [n*(1+P), D]      T(h) -- the first GEMM's operand and the upper half of the split residual stream;
  *   lo8   i8  [n*(1+P), D]      the lower part of the split stream: the next 8 bits of h's pattern relative to x16 (SLIME_EPI_BIAS_RESID_SPLIT_LN);
  *   stats f32 [n*(1+P), D/64, 2] (sum, sum of squares) of the ROUNDED rows per 64-column group (first folded LayerNorm).
- * Limits (checked here, by slime_vit_check at pack time and by every slime_vit_forward*): D in {128, 256, 1024};
- * image % patch == 0 and image % 8 == 0; image / patch <= 24 patches per side; 6 * patch * image < 65535; 16-bit pixels
- * must already be of type T (fp32 pixels are rounded on the way in).  CLIP-L/14-336 and -224 fit; a 448 / 14 tower does not. */
+ * Limits (checked here, by slime_vit_check at pack time and by every slime_vit_forward*): D in {128, 256, 768, 1024};
+ * image % patch == 0 and image % 8 == 0; image / patch <= 24 patches per side; 6 * patch * image < 65535; at most 160 KiB of LDS
+ * (staged image rows + the [48, kpad + 8] operand); 16-bit pixels must already be of type T (fp32 pixels are rounded on the way in).
+ * CLIP-L/14-336 and -224 and ViT-B/16-224 fit; a 448 / 14 tower (32 patches per side) and patch 32 (LDS) do not. */
 int slime_patch_embed_prenorm(const void* pixels, int pix_dtype, const void* patch_w_frag, const float* cls, const float* pos,
                               const float* ln_w, const float* ln_b, float eps, float* h, void* x16, void* lo8, float* stats,
                               int dtype, int n, int image, int patch, int kpad, int D, void* stream);
@@ -511,6 +514,18 @@ int slime_vit_forward_ksplit(const slime_vit_desc* d, const void* pixels, int pi
  * entry i = output of encoder layer i.  Run with a descriptor whose layers_run covers the last state wanted. */
 int slime_vit_forward_states(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n_crops, float* states_f32,
                              void* ws, size_t ws_bytes, void* stream);
+
+/* The superset of slime_vit_forward, _ksplit and _states, with the options a descriptor does not carry.  act = the MLP's activation
+ * (HF CLIPVisionConfig.hidden_act): SLIME_ACT_QUICKGELU (OpenAI CLIP) or SLIME_ACT_GELU (the erf GELU of the OpenCLIP towers:
+ * fc1 runs the LayerNorm-fold consumer with SLIME_EPI_BIAS_GELU_T).  out / hidden_f32 / states_f32: any may be NULL, one is
+ * required; ks NULL = unsplit.  ws: slime_vit_workspace_bytes, or slime_vit_ksplit_workspace_bytes with ks (the activation changes
+ * no buffer).  opts == NULL or act == SLIME_ACT_QUICKGELU makes the launches of the entries above, call for call (bit-identical);
+ * any other act is SLIME_EINVAL before the first launch, the value named in slime_last_error(). */
+enum { SLIME_ACT_QUICKGELU = 0, SLIME_ACT_GELU = 1 };
+typedef struct { int act; } slime_vit_opts;          /* NULL = all defaults = today's behaviour */
+int slime_vit_forward_opts(const slime_vit_desc* d, const slime_vit_opts* opts, const void* pixels, int pix_dtype, int n_crops,
+                           void* out, int out_dtype, int keep_cls, float* hidden_f32, float* states_f32,
+                           const slime_vit_ksplit* ks, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Resampler (sampler.py:91-173) with kv_proj = proj = Identity, as post_qformer / GatedBlock.attn

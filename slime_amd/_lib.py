@@ -88,6 +88,15 @@ class VitKsplit(C.Structure):
     _fields_ = [("qkv", c_int), ("out_proj", c_int), ("fc1", c_int), ("fc2", c_int)]
 
 
+ACT_QUICKGELU, ACT_GELU = 0, 1      # SLIME_ACT_*
+ACT_BY_NAME = {"quick_gelu": ACT_QUICKGELU, "gelu": ACT_GELU}       # HF CLIPVisionConfig.hidden_act -> SLIME_ACT_*
+
+
+class VitOpts(C.Structure):
+    """slime_vit_opts: what slime_vit_forward_opts takes beside the descriptor (the MLP's activation)."""
+    _fields_ = [("act", c_int)]
+
+
 class Probe(C.Structure):
     _fields_ = [("layer", c_int), ("kernel", c_int), ("start", c_void_p), ("stop", c_void_p)]
 
@@ -185,6 +194,8 @@ _SIGNATURES = {
     "slime_vit_ksplit_workspace_bytes": (c_size_t, [_P(VitDesc), c_int, _P(VitKsplit)]),
     "slime_vit_forward_ksplit": (c_int, [_P(VitDesc), c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, _P(VitKsplit), c_void_p,
                                          c_size_t, c_void_p]),
+    "slime_vit_forward_opts": (c_int, [_P(VitDesc), _P(VitOpts), c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                       _P(VitKsplit), c_void_p, c_size_t, c_void_p]),
     "slime_resampler_workspace_bytes": (c_size_t, [_P(ResamplerDesc), c_int]),
     "slime_resampler_forward": (c_int, [_P(ResamplerDesc), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                         c_size_t, c_void_p]),

@@ -95,7 +95,7 @@ int slime_patch_embed_geometry(int image, int patch, int kpad, int D, size_t* ld
 static int vit_validate(const slime_vit_desc* d) {
     SLIME_REQUIRE(d, "vit: null descriptor");
     SLIME_REQUIRE(is16(d->dtype), "vit: dtype must be BF16 or F16");
-    SLIME_REQUIRE(d->hidden == 128 || d->hidden == 256 || d->hidden == 1024, "vit: hidden=%d unsupported", d->hidden);
+    SLIME_REQUIRE(d->hidden == 128 || d->hidden == 256 || d->hidden == 768 || d->hidden == 1024, "vit: hidden=%d unsupported", d->hidden);
     SLIME_REQUIRE(d->hidden % 64 == 0, "vit: hidden must be a multiple of 64 (LayerNorm partial sums per 64 columns)");
     SLIME_REQUIRE(d->heads > 0 && d->hidden % d->heads == 0 && d->hidden / d->heads == 64, "vit: head_dim must be 64");
     SLIME_REQUIRE(d->inter % 128 == 0 && d->inter % 64 == 0, "vit: intermediate size %d must be a multiple of 128", d->inter);
@@ -145,7 +145,7 @@ static constexpr int g_vit_skip_mask = 0;
 
 static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out, int out_dtype, int keep_cls,
                    float* hidden_f32, void* ws, size_t ws_bytes, void* stream, const slime_probe* probe, float* states,
-                   const slime_vit_ksplit* ks = nullptr);
+                   const slime_vit_ksplit* ks = nullptr, int act = SLIME_ACT_QUICKGELU);
 
 extern "C" int slime_vit_forward_ex(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out,
                                     int out_dtype, int keep_cls, float* hidden_f32, void* ws, size_t ws_bytes,
@@ -191,9 +191,19 @@ extern "C" int slime_vit_forward_states(const slime_vit_desc* d, const void* pix
     return vit_run(d, pixels, pix_dtype, n, nullptr, SLIME_F32, 1, nullptr, ws, ws_bytes, stream, nullptr, states_f32);
 }
 
+// The superset of slime_vit_forward / _ksplit / _states, with the options a descriptor does not carry (the MLP's activation).
+extern "C" int slime_vit_forward_opts(const slime_vit_desc* d, const slime_vit_opts* opts, const void* pixels, int pix_dtype, int n,
+                                      void* out, int out_dtype, int keep_cls, float* hidden_f32, float* states_f32,
+                                      const slime_vit_ksplit* ks, void* ws, size_t ws_bytes, void* stream) {
+    const int act = opts ? opts->act : SLIME_ACT_QUICKGELU;
+    SLIME_REQUIRE(act == SLIME_ACT_QUICKGELU || act == SLIME_ACT_GELU, "vit_forward_opts: act=%d is neither SLIME_ACT_QUICKGELU (0) nor "
+                                                                       "SLIME_ACT_GELU (1)", act);
+    return vit_run(d, pixels, pix_dtype, n, out, out_dtype, keep_cls, hidden_f32, ws, ws_bytes, stream, nullptr, states_f32, ks, act);
+}
+
 static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out, int out_dtype, int keep_cls,
                    float* hidden_f32, void* ws, size_t ws_bytes, void* stream, const slime_probe* probe, float* states,
-                   const slime_vit_ksplit* ks) {
+                   const slime_vit_ksplit* ks, int act) {
     TRY(vit_validate(d));
     SLIME_REQUIRE(pixels && n > 0, "vit: bad input");
     SLIME_REQUIRE(out || hidden_f32 || states, "vit: no output requested");
@@ -261,11 +271,11 @@ static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, i
         resid_update(ga);
         ga.B_frag = layer_w(d->w_o_frag, (size_t)D * D);
         PROBED(3, layer_gemm(ga, sp.out_proj));
-        // ff = quick_gelu(LN2(h) W1^T + b)  (HF :379-380, :346-350)
+        // ff = act(LN2(h) W1^T + b), act = quick_gelu or the erf GELU of the OpenCLIP towers  (HF :379-380, :346-350)
         ga = slime_gemm_args{};
         ga.M = M; ga.dtype = dt; ga.ln_eps = d->eps;
         ga.A = xn; ga.lda = D; ga.B = layer_w(d->w_fc1, (size_t)F * D); ga.bias = d->b_fc1 + (size_t)l * F; ga.C = ff; ga.ldc = F; ga.N = F; ga.K = D;
-        ga.epilogue = SLIME_EPI_BIAS_QUICKGELU_T; ga.ln_stats = stats; ga.ln_groups = G; ga.ln_colsum = d->colsum_fc1 + (size_t)l * F;
+        ga.epilogue = act == SLIME_ACT_GELU ? SLIME_EPI_BIAS_GELU_T : SLIME_EPI_BIAS_QUICKGELU_T; ga.ln_stats = stats; ga.ln_groups = G; ga.ln_colsum = d->colsum_fc1 + (size_t)l * F;
         ga.B_frag = layer_w(d->w_fc1_frag, (size_t)F * D);
         PROBED(5, layer_gemm(ga, sp.fc1));
         // h += ff W2^T + b; prepares the next layer's LN1  (HF :381-383)
@@ -368,7 +378,7 @@ extern "C" int slime_resampler_forward(const slime_resampler_desc* d, const floa
 static int mlp_validate(const slime_mlp_desc* d) {
     SLIME_REQUIRE(d, "mlp: null descriptor");
     SLIME_REQUIRE(is16(d->dtype), "mlp: dtype must be BF16 or F16");
-    SLIME_REQUIRE(d->in_dim == 128 || d->in_dim == 256 || d->in_dim == 1024, "mlp: in_dim=%d unsupported", d->in_dim);
+    SLIME_REQUIRE(d->in_dim == 128 || d->in_dim == 256 || d->in_dim == 768 || d->in_dim == 1024, "mlp: in_dim=%d unsupported", d->in_dim);
     SLIME_REQUIRE(d->hidden % 128 == 0, "mlp: hidden=%d must be a multiple of 128", d->hidden);
     SLIME_REQUIRE((d->w1 || d->w1_frag) && d->b1 && (d->w2 || d->w2_frag) && d->b2, "mlp: missing weights (row-major or fragment-order)");
     return SLIME_OK;

@@ -138,7 +138,7 @@ __device__ __forceinline__ void epilogue_wave(const GemmArgs& g, f32x4 (&acc)[MI
     }
     auto in_range = [&](int row) { return FULL || row < g.M; };
     if constexpr (LN) {
-        // LayerNorm-fold epilogues (BIAS_T / BIAS_QUICKGELU_T only): pre-activation = rstd[m] * (acc - mu[m] * colsum[n]) + bias[n],
+        // LayerNorm-fold epilogues (BIAS_T / BIAS_QUICKGELU_T / BIAS_GELU_T): pre-activation = rstd[m] * (acc - mu[m] * colsum[n]) + bias[n],
         // evaluated as fma(rstd, acc, fma(-mu rstd, colsum, bias)).  Everything that is loaded (bias, colsum, the row table) is
         // fetched up front; each 8-column group is then read from the accumulators, finished and stored at once, so only 8
         // results are live at a time (the in-place form below keeps all of them in VGPRs, which spills next to 64 constants).
@@ -180,6 +180,11 @@ __device__ __forceinline__ void epilogue_wave(const GemmArgs& g, f32x4 (&acc)[MI
                         const f32x2 y = z * r;
                         v[j] = y[0]; v[j + 1] = y[1];
                     }
+                } else if constexpr (EPI == SLIME_EPI_BIAS_GELU_T) {
+                    // erf GELU of the folded pre-activation (towers with hidden_act 'gelu'): the arithmetic of the un-folded BIAS_GELU_T
+                    // epilogue below, element by element; the group is stored before the next one is formed
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] = gelu_erf(v[j]);
                 }
                 const u32x4 w = pack8<T>(v);
                 if (in_range(row))
@@ -463,11 +468,11 @@ __device__ __forceinline__ void epilogue_mix(const GemmArgs& g, f32x4 (&acc)[8][
 }
 
 // Epilogue dispatch shared by every kernel: FULL-tile fast path or ragged last row tile; LayerNorm-fold variant when the call
-// carries row statistics (only the two epilogues the tower uses it with are instantiated).
+// carries row statistics (only the three epilogues the tower uses it with are instantiated).
 template <typename T, int EPI, int MI, int NI>
 __device__ __forceinline__ void run_epilogue(const GemmArgs& g, f32x4 (&acc)[MI][NI], const int row_base, const int col_base,
                                              const bool full, const float* lnrow_lane) {
-    constexpr bool CAN_LN = (EPI == SLIME_EPI_BIAS_T || EPI == SLIME_EPI_BIAS_QUICKGELU_T);
+    constexpr bool CAN_LN = (EPI == SLIME_EPI_BIAS_T || EPI == SLIME_EPI_BIAS_QUICKGELU_T || EPI == SLIME_EPI_BIAS_GELU_T);
     if constexpr (CAN_LN) {
         if (g.ln_stats) {
             if (full) epilogue_wave<T, EPI, MI, NI, true, true>(g, acc, row_base, col_base, lnrow_lane);
@@ -1528,8 +1533,8 @@ static int gemm_check_args(const slime_gemm_args* a, GemmArgs& out) {
     SLIME_REQUIRE(((uintptr_t)a->A % 16 == 0) && ((uintptr_t)a->B % 16 == 0) && ((uintptr_t)a->C % 16 == 0) &&
                   (!a->bias || (uintptr_t)a->bias % 16 == 0), "gemm: pointers must be 16-byte aligned");
     if (a->ln_stats) {
-        SLIME_REQUIRE(a->epilogue == SLIME_EPI_BIAS_T || a->epilogue == SLIME_EPI_BIAS_QUICKGELU_T,
-                      "gemm: the LayerNorm fold is built for the BIAS_T / BIAS_QUICKGELU_T epilogues");
+        SLIME_REQUIRE(a->epilogue == SLIME_EPI_BIAS_T || a->epilogue == SLIME_EPI_BIAS_QUICKGELU_T || a->epilogue == SLIME_EPI_BIAS_GELU_T,
+                      "gemm: the LayerNorm fold is built for the BIAS_T / BIAS_QUICKGELU_T / BIAS_GELU_T epilogues");
         SLIME_REQUIRE(a->ln_colsum && a->ln_groups > 0 && ((uintptr_t)a->ln_colsum % 16) == 0 && ((uintptr_t)a->ln_stats % 16) == 0,
                       "gemm: LayerNorm fold needs ln_colsum [N] and ln_groups partial sums per row (16-byte aligned)");
         SLIME_REQUIRE(a->ln_groups * 64 == K, "gemm: LayerNorm fold: ln_groups=%d partial sums of 64 columns must cover K=%d", a->ln_groups, K);

@@ -335,9 +335,10 @@ int launch_pe_d(const PEArgs& a, int D, size_t lds, hipStream_t s) {
     switch (D) {
         case 128: return launch_pe<T, PixT, 128, 2>(a, lds, s);
         case 256: return launch_pe<T, PixT, 256, 4>(a, lds, s);
+        case 768: return launch_pe<T, PixT, 768, 6>(a, lds, s);        // six waves of 128 columns, as at 1024 (ViT-B widths)
         case 1024: return launch_pe<T, PixT, 1024, 8>(a, lds, s);
     }
-    slime_set_error("patch_embed: D=%d unsupported (128, 256, 1024)", D);
+    slime_set_error("patch_embed: D=%d unsupported (128, 256, 768, 1024)", D);
     return SLIME_EINVAL;
 }
 
@@ -350,13 +351,13 @@ int slime_patch_embed_geometry(int image, int patch, int kpad, int D, size_t* ld
     SLIME_REQUIRE(patch > 0 && image > 0 && image % patch == 0 && image % 8 == 0,
                   "patch_embed: image %d must be a multiple of the patch %d and of 8 (16-byte pixel pieces)", image, patch);
     SLIME_REQUIRE(kpad % 64 == 0 && kpad >= 3 * patch * patch, "patch_embed: kpad=%d (3 * patch^2 rounded up to a multiple of 64)", kpad);
-    SLIME_REQUIRE(D == 128 || D == 256 || D == 1024, "patch_embed: D=%d unsupported (128, 256, 1024)", D);
+    SLIME_REQUIRE(D == 128 || D == 256 || D == 768 || D == 1024, "patch_embed: D=%d unsupported (128, 256, 768, 1024)", D);
     const int g = image / patch;
     SLIME_REQUIRE(2 * g <= PE_ROWS, "patch_embed: %d patches per side -- the front end holds two rows of at most %d patches per workgroup "
                   "(CLIP-L/14-336: 24; a 448 / 14 tower would need 32)", g, PE_ROWS / 2);
     SLIME_REQUIRE((size_t)6 * patch * image < 65535, "patch_embed: 6 * patch * image = %zu elements of staged image rows exceed the 16-bit offset table",
                   (size_t)6 * patch * image);
-    const int nw = D == 128 ? 2 : D == 256 ? 4 : 8;
+    const int nw = D == 128 ? 2 : D == 256 ? 4 : D == 768 ? 6 : 8;            // launch_pe_d's waves: one [PE_ROWS] reduction row each
     const size_t lds = pe_align16((size_t)6 * patch * image * 2) + (size_t)PE_ROWS * (kpad + 8) * 2 + pe_align16((size_t)kpad * 2) +
                        (size_t)nw * PE_ROWS * sizeof(float);
     SLIME_REQUIRE(lds <= 160 * 1024, "patch_embed: %zu bytes of LDS needed (160 KiB per CU)", lds);

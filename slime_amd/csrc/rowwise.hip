@@ -116,8 +116,9 @@ static int launch_ln(const LnArgs& a, int D, hipStream_t s) {
     switch (D) {
         case 128: hipLaunchKernelGGL((layernorm_kernel<T, 2>), grid, block, 0, s, a); break;
         case 256: hipLaunchKernelGGL((layernorm_kernel<T, 4>), grid, block, 0, s, a); break;
+        case 768: hipLaunchKernelGGL((layernorm_kernel<T, 12>), grid, block, 0, s, a); break;
         case 1024: hipLaunchKernelGGL((layernorm_kernel<T, 16>), grid, block, 0, s, a); break;
-        default: slime_set_error("layernorm: D=%d unsupported (128, 256, 1024)", D); return SLIME_EINVAL;
+        default: slime_set_error("layernorm: D=%d unsupported (128, 256, 768, 1024)", D); return SLIME_EINVAL;
     }
     SLIME_CHECK_LAUNCH("layernorm");
     return SLIME_OK;
@@ -220,8 +221,9 @@ static int launch_ln_indexed(const LnIndexedArgs& a, int D, hipStream_t s) {
     switch (D) {
         case 128: hipLaunchKernelGGL((layernorm_indexed_kernel<T, 2>), grid, block, 0, s, a); break;
         case 256: hipLaunchKernelGGL((layernorm_indexed_kernel<T, 4>), grid, block, 0, s, a); break;
+        case 768: hipLaunchKernelGGL((layernorm_indexed_kernel<T, 12>), grid, block, 0, s, a); break;
         case 1024: hipLaunchKernelGGL((layernorm_indexed_kernel<T, 16>), grid, block, 0, s, a); break;
-        default: slime_set_error("layernorm: D=%d unsupported (128, 256, 1024)", D); return SLIME_EINVAL;
+        default: slime_set_error("layernorm: D=%d unsupported (128, 256, 768, 1024)", D); return SLIME_EINVAL;
     }
     SLIME_CHECK_LAUNCH("layernorm_indexed");
     return SLIME_OK;

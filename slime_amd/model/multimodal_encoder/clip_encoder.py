@@ -127,7 +127,7 @@ class HipCLIPVisionModel(nn.Module):
         if key not in self._packed:
             base = self._packed.get((select_layer, self.operand_dtype(), str(self.device), 0))
             if base is not None:                   # extra slots share the weights, own a workspace
-                self._packed[key] = ops.PackedTower(base.cfg, base.dtype, base.layers_run, base.tensors, base.desc)
+                self._packed[key] = ops.PackedTower(base.cfg, base.dtype, base.layers_run, base.tensors, base.desc, act=base.act)
             else:
                 self._packed[key] = ops.pack_tower(self.state_dict(), self.config, self.operand_dtype(), self.device,
                                                    select_layer)
@@ -259,8 +259,7 @@ class CLIPVisionTower(nn.Module):
             path = _resolve_local(name)
             cfg, sd = _read_hf_vision_config(path), _read_hf_weights(path)
             self.image_processor = ClipImageProcessor.from_pretrained(path)
-        if cfg.hidden_act != "quick_gelu":
-            raise ValueError(f"unsupported CLIP activation {cfg.hidden_act!r}: the HIP tower implements quick_gelu")
+        ops.tower_act(cfg)          # quick_gelu (OpenAI CLIP) or gelu (OpenCLIP); anything else (gelu_new, ...) is refused by name
         self.vision_tower = HipCLIPVisionModel(cfg, self._compute_dtype)
         check_tower_keys(self.vision_tower.load_state_dict(sd, strict=False), name)
         if device_map not in (None, "auto") and not isinstance(device_map, dict):

@@ -296,10 +296,20 @@ class PackedTower:
     desc: _lib.VitDesc
     ws: Workspace = field(default_factory=Workspace)
     probe: Optional[tuple] = None        # (layer, kernel id, start event, stop event): in-situ kernel timing
+    act: int = _lib.ACT_QUICKGELU        # SLIME_ACT_* of cfg.hidden_act: anything but quick-GELU runs through slime_vit_forward_opts
 
     @property
     def device(self):
         return self.tensors["cls"].device
+
+
+def tower_act(cfg: VisionConfig) -> int:
+    """SLIME_ACT_* of ``cfg.hidden_act``; a tower with another activation is refused by name (no kernel computes it)."""
+    try:
+        return _lib.ACT_BY_NAME[cfg.hidden_act]
+    except KeyError:
+        raise ValueError(f"vision tower hidden_act={cfg.hidden_act!r} is not supported: the HIP path computes "
+                         f"{' and '.join(repr(k) for k in _lib.ACT_BY_NAME)} only") from None
 
 
 def layers_for_select(cfg: VisionConfig, select_layer: int) -> int:
@@ -391,6 +401,7 @@ def pack_tower(state_dict: Dict[str, torch.Tensor], cfg: VisionConfig, dtype: to
     ``device``, the four layer matrices and the conv weight also in MFMA-fragment order)."""
     if dtype not in (torch.bfloat16, torch.float16):
         raise ValueError("tower compute dtype must be bf16 or fp16 (MFMA operand type); fp32 I/O is supported")
+    act = tower_act(cfg)
     D, Fi, L = cfg.hidden_size, cfg.intermediate_size, layers_for_select(cfg, select_layer)
     kpad = (3 * cfg.patch_size * cfg.patch_size + 63) // 64 * 64
     T: Dict[str, torch.Tensor] = {k: v.to(device).contiguous() for k, v in tower_host_tensors(state_dict, cfg, dtype, select_layer).items()}
@@ -413,7 +424,7 @@ def pack_tower(state_dict: Dict[str, torch.Tensor], cfg: VisionConfig, dtype: to
     # the driver's own validation, at PACK time: a geometry the fused front end cannot run (more than 24 patches per side, image
     # not a multiple of 8, ...) is refused here with the limit named, not by the first forward
     _lib.check(_lib.load().slime_vit_check(C.byref(d)), "pack_tower")
-    return PackedTower(cfg, dtype, L, T, d)
+    return PackedTower(cfg, dtype, L, T, d, act=act)
 
 
 def tower_forward(pt: PackedTower, pixels: torch.Tensor, out_dtype: Optional[torch.dtype] = None,
@@ -423,7 +434,8 @@ def tower_forward(pt: PackedTower, pixels: torch.Tensor, out_dtype: Optional[tor
     a contiguous [N, P(+1), D] tensor or leading-dim slice of one).
     k_split = (qkv, out_proj, fc1, fc2): run those layer GEMMs as deterministic split-K pairs (slime_vit_forward_ksplit; 1 =
     unsplit).  None (the default) is slime_vit_forward_ex exactly.  For one setting the result does not depend on how the crops are
-    cut into calls; it is not bit-identical to another setting's."""
+    cut into calls; it is not bit-identical to another setting's.
+    A tower whose activation is not quick-GELU (``pt.act``) makes the same passes through slime_vit_forward_opts."""
     lib = _lib.load()
     _require_cuda(pixels, "pixels")
     cfg = pt.cfg
@@ -449,12 +461,20 @@ def tower_forward(pt: PackedTower, pixels: torch.Tensor, out_dtype: Optional[tor
         ks = _lib.VitKsplit(*(int(v) for v in k_split))
         need = lib.slime_vit_ksplit_workspace_bytes(C.byref(pt.desc), n, C.byref(ks))
         base, avail = pt.ws.aligned(need, pixels.device)
+        if pt.act != _lib.ACT_QUICKGELU:
+            _tower_opts_call(lib, pt, pixels, n, out, out_dtype, keep_cls, hidden, None, ks, base, avail)
+            return (out, hidden) if want_hidden else out
         _lib.check(lib.slime_vit_forward_ksplit(C.byref(pt.desc), pixels.data_ptr(), dtype_code(pixels.dtype), n, out.data_ptr(),
                                                 dtype_code(out_dtype), int(keep_cls), _ptr(hidden), C.byref(ks), base,
                                                 avail, _stream()), "slime_vit_forward_ksplit")
         return (out, hidden) if want_hidden else out
     need = lib.slime_vit_workspace_bytes(C.byref(pt.desc), n)
     base, avail = pt.ws.aligned(need, pixels.device)
+    if pt.act != _lib.ACT_QUICKGELU:
+        if pt.probe is not None:
+            raise ValueError("tower_forward: the timing probe (slime_vit_forward_ex) is built for quick-GELU towers")
+        _tower_opts_call(lib, pt, pixels, n, out, out_dtype, keep_cls, hidden, None, None, base, avail)
+        return (out, hidden) if want_hidden else out
     probe = None
     if pt.probe is not None:
         layer, kernel, e0, e1 = pt.probe
@@ -463,6 +483,14 @@ def tower_forward(pt: PackedTower, pixels: torch.Tensor, out_dtype: Optional[tor
                                         dtype_code(out_dtype), int(keep_cls), _ptr(hidden), base,
                                         avail, _stream(), probe), "slime_vit_forward")
     return (out, hidden) if want_hidden else out
+
+
+def _tower_opts_call(lib, pt: PackedTower, pixels, n, out, out_dtype, keep_cls, hidden, states, ks, base, avail) -> None:
+    """slime_vit_forward_opts with the tower's activation: the one entry that takes it (any of out / hidden / states, optional k-split)."""
+    opts = _lib.VitOpts(pt.act)
+    _lib.check(lib.slime_vit_forward_opts(C.byref(pt.desc), C.byref(opts), pixels.data_ptr(), dtype_code(pixels.dtype), n, _ptr(out),
+                                          dtype_code(out_dtype) if out is not None else _lib.F32, int(keep_cls), _ptr(hidden), _ptr(states),
+                                          C.byref(ks) if ks is not None else None, base, avail, _stream()), "slime_vit_forward_opts")
 
 
 def tower_hidden_states(pt: PackedTower, pixels: torch.Tensor) -> torch.Tensor:
@@ -479,6 +507,9 @@ def tower_hidden_states(pt: PackedTower, pixels: torch.Tensor) -> torch.Tensor:
     states = torch.empty((pt.layers_run + 1, n, cfg.seq_len, cfg.hidden_size), dtype=torch.float32, device=pixels.device)
     need = lib.slime_vit_workspace_bytes(C.byref(pt.desc), n)
     base, avail = pt.ws.aligned(need, pixels.device)
+    if pt.act != _lib.ACT_QUICKGELU:
+        _tower_opts_call(lib, pt, pixels, n, None, None, True, None, states, None, base, avail)
+        return states
     _lib.check(lib.slime_vit_forward_states(C.byref(pt.desc), pixels.data_ptr(), dtype_code(pixels.dtype), n, states.data_ptr(), base,
                                             avail, _stream()), "slime_vit_forward_states")
     return states
@@ -500,7 +531,7 @@ def tower_kernel_names(pt: PackedTower, n_crops: int) -> Dict[int, str]:
     resid_epi = _lib.load().slime_vit_residual_epilogue()      # what the tower launches for out_proj / fc2
     return {1: gemm_kernel_name(M, 3 * D, D, pt.dtype, _lib.EPI_BIAS_T, fr["w_qkv"]),
             2: f"attn64r_kernel<{t}, 3>" if 321 <= cfg.seq_len <= 608 and cfg.head_dim == 64 else f"attn_kernel<{t}, 64, 608, 8, 5>",
-            5: gemm_kernel_name(M, Fi, D, pt.dtype, _lib.EPI_BIAS_QUICKGELU_T, fr["w_fc1"]),
+            5: gemm_kernel_name(M, Fi, D, pt.dtype, _lib.EPI_BIAS_GELU_T if pt.act == _lib.ACT_GELU else _lib.EPI_BIAS_QUICKGELU_T, fr["w_fc1"]),
             3: gemm_kernel_name(M, D, D, pt.dtype, resid_epi, fr["w_o"]),
             6: gemm_kernel_name(M, D, Fi, pt.dtype, resid_epi, fr["w_fc2"])}
 

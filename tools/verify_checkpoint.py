@@ -93,7 +93,28 @@ def make_crops(enc, image_path, size, seed):
     return px, img.size, src
 
 
+class oracle_activation:
+    """The oracle's tower restates OpenAI CLIP (quick-GELU) and is pinned; an OpenCLIP tower (hidden_act 'gelu') is the same
+    arithmetic with nn.GELU() in the MLP (HF ACT2FN['gelu']), so for the duration of a report the oracle's activation is that one."""
+
+    def __init__(self, hidden_act: str):
+        from oracle import slime_oracle as O
+        self.O, self.act = O, {"quick_gelu": O.quick_gelu, "gelu": torch.nn.functional.gelu}[hidden_act]
+
+    def __enter__(self):
+        self.saved, self.O.quick_gelu = self.O.quick_gelu, self.act
+
+    def __exit__(self, *exc):
+        self.O.quick_gelu = self.saved
+        return False
+
+
 def oracle_report(tsd, asd, vcfg, acfg, px, image_size, select_layer=-2):
+    with oracle_activation(vcfg.hidden_act):
+        return _oracle_report(tsd, asd, vcfg, acfg, px, image_size, select_layer)
+
+
+def _oracle_report(tsd, asd, vcfg, acfg, px, image_size, select_layer):
     from oracle import slime_oracle as O
     t0 = time.perf_counter()
     L = vcfg.num_hidden_layers
@@ -150,7 +171,7 @@ def main(argv=None):
 
     enc, tsd, asd, vcfg, acfg, notes = load_models(args.clip_dir, args.ckpt, args.seed)
     px, image_size, src = make_crops(enc, args.image, tuple(args.size), args.seed)
-    print(f"tower : {args.clip_dir}: ViT {vcfg.hidden_size} x {vcfg.num_hidden_layers} layers, {vcfg.image_size}/{vcfg.patch_size}, {len(tsd)} tensors")
+    print(f"tower : {args.clip_dir}: ViT {vcfg.hidden_size} x {vcfg.num_hidden_layers} layers, {vcfg.image_size}/{vcfg.patch_size}, {vcfg.hidden_act}, {len(tsd)} tensors")
     for n in notes:
         print(n)
     print(f"image : {src} -> {px.shape[0]} crops (1 global + {px.shape[0] - 1} local)")
