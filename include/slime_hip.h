@@ -64,6 +64,10 @@ enum {
                                    * sign -- noise far below what a LayerNorm statistic resolves, stated here because both feed the same fold).
                                    * C is at once the upper part of the stream and the next GEMM's operand (no separate x16 copy). */
 };
+/* ... and the tanh-form GELU (F.gelu(approximate='tanh'), HF "gelu_pytorch_tanh": fc1 of the SigLIP towers), evaluated as
+ * x * sigmoid(2 sqrt(2 / pi) (x + 0.044715 x^3)) = 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))) -> T.  Built as the
+ * LayerNorm-fold consumer (ln_stats) and without the fold, in every kernel family and in slime_gemm_ksplit. */
+enum { SLIME_EPI_BIAS_GELU_TANH_T = 9 };
 
 int slime_abi_version(void);
 const char* slime_last_error(void);
@@ -179,6 +183,14 @@ int slime_layernorm(const float* x, int ldx, int rows, int D, const float* w, co
 int slime_patch_embed_prenorm(const void* pixels, int pix_dtype, const void* patch_w_frag, const float* cls, const float* pos,
                               const float* ln_w, const float* ln_b, float eps, float* h, void* x16, void* lo8, float* stats,
                               int dtype, int n, int image, int patch, int kpad, int D, void* stream);
+
+/* The front end's second form, for towers without class token and without pre-LayerNorm (HF SiglipVisionEmbeddings):
+ *   h[n, P, D] = conv_{patch x patch, stride patch}(pixels) + pos'[P, D],   pos' = position_embedding + patch_embedding.bias
+ * (the conv bias is added to the position table once, at pack time, in fp32).  Output row = patch index: nothing writes a class row.
+ * Same staging, re-tiling and MFMA loop, same outputs (h / x16 / lo8 / stats over n*P rows, stats = partial sums of the ROUNDED rows)
+ * and the same geometry limits as slime_patch_embed_prenorm.  Patch 16 gives kpad = 3 * 16^2 = 768 exactly (no zero K columns). */
+int slime_patch_embed_plain(const void* pixels, int pix_dtype, const void* patch_w_frag, const float* pos, float* h, void* x16,
+                            void* lo8, float* stats, int dtype, int n, int image, int patch, int kpad, int D, void* stream);
 
 /* Fused multi-head attention, softmax(Q K^T) V with fp32 online softmax; Q is expected PRE-SCALED
  * by head_dim^-0.5 * log2(e) (SLIME_ATTN_Q_PRESCALE, folded into the q projection weights and bias at pack
@@ -526,6 +538,23 @@ typedef struct { int act; } slime_vit_opts;          /* NULL = all defaults = to
 int slime_vit_forward_opts(const slime_vit_desc* d, const slime_vit_opts* opts, const void* pixels, int pix_dtype, int n_crops,
                            void* out, int out_dtype, int keep_cls, float* hidden_f32, float* states_f32,
                            const slime_vit_ksplit* ks, void* ws, size_t ws_bytes, void* stream);
+
+/* SigLIP vision towers (HF SiglipVisionModel, patch 16, head_dim 64): the layer loop of slime_vit_forward* over a sequence of
+ * S = P rows -- no class token, no pre-LayerNorm --, behind slime_patch_embed_plain, with fc1's epilogue SLIME_EPI_BIAS_GELU_TANH_T.
+ * They take slime_vit_desc with these conventions: cls, pre_ln_w and pre_ln_b MUST be NULL (refused otherwise, the field named);
+ * pos is pos' f32 [P, D] = position_embedding + patch_embedding.bias; every other field as for the CLIP entries (LayerNorm gamma /
+ * beta folded into w_qkv / w_fc1, the colsums, the fragment-order images).  post_layernorm and the pooling head are never run.
+ *   out        [n, P, D] of out_dtype: all P rows of the last state run;
+ *   hidden_f32 [n, P, D]: the same state in fp32;
+ *   states_f32 [layers_run + 1, n, P, D]: HF's hidden_states (entry 0 = the embeddings, entry i = after layer i).
+ * Any of the three may be NULL, one is required.  ks NULL = unsplit (slime_gemm_ex); otherwise the layer GEMMs run through
+ * slime_gemm_ksplit as in slime_vit_forward_ksplit.  ws: slime_siglip_workspace_bytes, or slime_siglip_ksplit_workspace_bytes
+ * with ks.  slime_siglip_check: the host-only validation every forward starts with (callers run it at pack time). */
+int slime_siglip_check(const slime_vit_desc* d);
+size_t slime_siglip_workspace_bytes(const slime_vit_desc* d, int n_crops);
+size_t slime_siglip_ksplit_workspace_bytes(const slime_vit_desc* d, int n_crops, const slime_vit_ksplit* ks);
+int slime_siglip_forward(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n_crops, void* out, int out_dtype,
+                         float* hidden_f32, float* states_f32, const slime_vit_ksplit* ks, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Resampler (sampler.py:91-173) with kv_proj = proj = Identity, as post_qformer / GatedBlock.attn

@@ -29,6 +29,7 @@ ABI_VERSION = 7
 BF16, F16, F32, U8 = 0, 1, 2, 3
 (EPI_BIAS_T, EPI_BIAS_QUICKGELU_T, EPI_BIAS_GELU_T, EPI_BIAS_F32, EPI_BIAS_RESID_F32, EPI_BIAS_RESID_F32_LN, EPI_BIAS_RESID_T,
  EPI_BIAS_GELU_MIX_T, EPI_BIAS_RESID_SPLIT_LN) = range(9)
+EPI_BIAS_GELU_TANH_T = 9   # declared in an enum of its own (include/slime_hip.h): the tanh-form GELU of the SigLIP towers
 
 GEMM_KSPLIT_MAX = 8        # SLIME_GEMM_KSPLIT_MAX
 
@@ -137,6 +138,8 @@ _SIGNATURES = {
     "slime_gemm_b_frag_usable": (c_int, [c_int, c_int]),
     "slime_patch_embed_prenorm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "slime_patch_embed_plain": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                        c_int, c_int, c_int, c_void_p]),
     "slime_gemm_ex": (c_int, [_P(GemmArgs), c_void_p]),
     "slime_gemm_ksplit_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "slime_gemm_ksplit": (c_int, [_P(GemmArgs), c_int, c_void_p, c_size_t, c_void_p]),
@@ -196,6 +199,11 @@ _SIGNATURES = {
                                          c_size_t, c_void_p]),
     "slime_vit_forward_opts": (c_int, [_P(VitDesc), _P(VitOpts), c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                        _P(VitKsplit), c_void_p, c_size_t, c_void_p]),
+    "slime_siglip_check": (c_int, [_P(VitDesc)]),
+    "slime_siglip_workspace_bytes": (c_size_t, [_P(VitDesc), c_int]),
+    "slime_siglip_ksplit_workspace_bytes": (c_size_t, [_P(VitDesc), c_int, _P(VitKsplit)]),
+    "slime_siglip_forward": (c_int, [_P(VitDesc), c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, _P(VitKsplit), c_void_p,
+                                     c_size_t, c_void_p]),
     "slime_resampler_workspace_bytes": (c_size_t, [_P(ResamplerDesc), c_int]),
     "slime_resampler_forward": (c_int, [_P(ResamplerDesc), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                         c_size_t, c_void_p]),

@@ -67,8 +67,13 @@ struct VitPlan {
     size_t xn, qkv, ctx, ff, lo, stats, total;  // offsets (lo: the lower part of the split stream, one byte per element)
 };
 
-static VitPlan vit_plan(const slime_vit_desc* d, int n) {
-    const int g = d->image / d->patch, P = g * g, S = P + 1;
+// The two tower forms the layer loop serves (vit_run): the CLIP layout (class token + pre-LayerNorm, S = P + 1 rows per crop) and the
+// plain one of the SigLIP towers (S = P rows behind slime_patch_embed_plain, fc1 with the tanh-form GELU).
+struct VitForm { bool plain; int fc1_epilogue; };
+static int vit_seq(const slime_vit_desc* d, bool plain) { const int g = d->image / d->patch; return g * g + (plain ? 0 : 1); }
+
+static VitPlan vit_plan(const slime_vit_desc* d, int n, bool plain = false) {
+    const int S = vit_seq(d, plain);
     const size_t M = (size_t)n * S, D = d->hidden;
     VitPlan p{};
     size_t off = 0;
@@ -92,8 +97,13 @@ static VitPlan vit_plan(const slime_vit_desc* d, int n) {
 
 int slime_patch_embed_geometry(int image, int patch, int kpad, int D, size_t* lds_out);   // patch_embed.hip: the fused front end's limits
 
-static int vit_validate(const slime_vit_desc* d) {
+static int vit_validate(const slime_vit_desc* d, bool plain = false) {
     SLIME_REQUIRE(d, "vit: null descriptor");
+    if (plain) {                                    // the SigLIP entries: the descriptor's class-token / pre-LayerNorm fields stay empty
+        SLIME_REQUIRE(!d->cls, "siglip: cls must be NULL (a SigLIP tower has no class token; slime_vit_forward* run the CLIP layout)");
+        SLIME_REQUIRE(!d->pre_ln_w, "siglip: pre_ln_w must be NULL (a SigLIP tower has no pre-LayerNorm)");
+        SLIME_REQUIRE(!d->pre_ln_b, "siglip: pre_ln_b must be NULL (a SigLIP tower has no pre-LayerNorm)");
+    }
     SLIME_REQUIRE(is16(d->dtype), "vit: dtype must be BF16 or F16");
     SLIME_REQUIRE(d->hidden == 128 || d->hidden == 256 || d->hidden == 768 || d->hidden == 1024, "vit: hidden=%d unsupported", d->hidden);
     SLIME_REQUIRE(d->hidden % 64 == 0, "vit: hidden must be a multiple of 64 (LayerNorm partial sums per 64 columns)");
@@ -102,7 +112,7 @@ static int vit_validate(const slime_vit_desc* d) {
     SLIME_REQUIRE(d->patch > 0 && d->image % d->patch == 0, "vit: image %d not a multiple of patch %d", d->image, d->patch);
     TRY(slime_patch_embed_geometry(d->image, d->patch, d->kpad, d->hidden, nullptr));      // the one-launch front end's geometry limits
     SLIME_REQUIRE(d->layers_run >= 0, "vit: layers_run < 0");
-    SLIME_REQUIRE(d->patch_w_frag && d->cls && d->pos && d->pre_ln_w && d->pre_ln_b,
+    SLIME_REQUIRE(d->patch_w_frag && d->pos && (plain || (d->cls && d->pre_ln_w && d->pre_ln_b)),
                   "vit: missing embedding weights (patch_w_frag = slime_gemm_pack_b of the conv weight is required since ABI 5)");
     // a per-layer weight is given as its fragment-order image, its row-major image, or both (slime_gemm_b_frag_usable)
     SLIME_REQUIRE(d->layers_run == 0 || ((d->w_qkv || d->w_qkv_frag) && d->b_qkv && d->colsum_qkv && (d->w_o || d->w_o_frag) && d->b_o &&
@@ -145,7 +155,7 @@ static constexpr int g_vit_skip_mask = 0;
 
 static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out, int out_dtype, int keep_cls,
                    float* hidden_f32, void* ws, size_t ws_bytes, void* stream, const slime_probe* probe, float* states,
-                   const slime_vit_ksplit* ks = nullptr, int act = SLIME_ACT_QUICKGELU);
+                   const slime_vit_ksplit* ks = nullptr, VitForm form = VitForm{false, SLIME_EPI_BIAS_QUICKGELU_T});
 
 extern "C" int slime_vit_forward_ex(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out,
                                     int out_dtype, int keep_cls, float* hidden_f32, void* ws, size_t ws_bytes,
@@ -164,8 +174,8 @@ static int vit_ksplit_validate(const slime_vit_desc* d, const slime_vit_ksplit* 
     return SLIME_OK;
 }
 
-static size_t vit_ksplit_partial_bytes(const slime_vit_desc* d, int n, const slime_vit_ksplit* ks) {
-    const int g = d->image / d->patch, M = n * (g * g + 1);
+static size_t vit_ksplit_partial_bytes(const slime_vit_desc* d, int n, const slime_vit_ksplit* ks, bool plain = false) {
+    const int M = n * vit_seq(d, plain);
     size_t b = slime_gemm_ksplit_workspace_bytes(M, 3 * d->hidden, ks->qkv);
     auto grow = [&](size_t x) { if (x > b) b = x; };
     grow(slime_gemm_ksplit_workspace_bytes(M, d->hidden, ks->out_proj));
@@ -198,19 +208,40 @@ extern "C" int slime_vit_forward_opts(const slime_vit_desc* d, const slime_vit_o
     const int act = opts ? opts->act : SLIME_ACT_QUICKGELU;
     SLIME_REQUIRE(act == SLIME_ACT_QUICKGELU || act == SLIME_ACT_GELU, "vit_forward_opts: act=%d is neither SLIME_ACT_QUICKGELU (0) nor "
                                                                        "SLIME_ACT_GELU (1)", act);
-    return vit_run(d, pixels, pix_dtype, n, out, out_dtype, keep_cls, hidden_f32, ws, ws_bytes, stream, nullptr, states_f32, ks, act);
+    return vit_run(d, pixels, pix_dtype, n, out, out_dtype, keep_cls, hidden_f32, ws, ws_bytes, stream, nullptr, states_f32, ks,
+                   VitForm{false, act == SLIME_ACT_GELU ? SLIME_EPI_BIAS_GELU_T : SLIME_EPI_BIAS_QUICKGELU_T});
+}
+
+// SigLIP towers: vit_run's layer loop in its plain form (include/slime_hip.h)
+extern "C" int slime_siglip_check(const slime_vit_desc* d) { return vit_validate(d, true); }
+
+extern "C" size_t slime_siglip_workspace_bytes(const slime_vit_desc* d, int n_crops) {
+    if (!d || n_crops <= 0 || d->patch <= 0) return 0;
+    return vit_plan(d, n_crops, true).total;
+}
+
+extern "C" size_t slime_siglip_ksplit_workspace_bytes(const slime_vit_desc* d, int n_crops, const slime_vit_ksplit* ks) {
+    if (!d || !ks || n_crops <= 0 || d->patch <= 0) return 0;
+    return vit_plan(d, n_crops, true).total + vit_ksplit_partial_bytes(d, n_crops, ks, true);
+}
+
+extern "C" int slime_siglip_forward(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out, int out_dtype,
+                                    float* hidden_f32, float* states_f32, const slime_vit_ksplit* ks, void* ws, size_t ws_bytes,
+                                    void* stream) {
+    return vit_run(d, pixels, pix_dtype, n, out, out_dtype, 1, hidden_f32, ws, ws_bytes, stream, nullptr, states_f32, ks,
+                   VitForm{true, SLIME_EPI_BIAS_GELU_TANH_T});
 }
 
 static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out, int out_dtype, int keep_cls,
                    float* hidden_f32, void* ws, size_t ws_bytes, void* stream, const slime_probe* probe, float* states,
-                   const slime_vit_ksplit* ks, int act) {
-    TRY(vit_validate(d));
+                   const slime_vit_ksplit* ks, VitForm form) {
+    TRY(vit_validate(d, form.plain));
     SLIME_REQUIRE(pixels && n > 0, "vit: bad input");
     SLIME_REQUIRE(out || hidden_f32 || states, "vit: no output requested");
     SLIME_REQUIRE(!out || out_dtype == SLIME_F32 || is16(out_dtype), "vit: bad out dtype");
     if (ks) TRY(vit_ksplit_validate(d, ks));
-    const VitPlan p = vit_plan(d, n);
-    const size_t part_bytes = ks ? vit_ksplit_partial_bytes(d, n, ks) : 0;      // one region of partial products behind the plan
+    const VitPlan p = vit_plan(d, n, form.plain);
+    const size_t part_bytes = ks ? vit_ksplit_partial_bytes(d, n, ks, form.plain) : 0;      // one region of partial products behind the plan
     TRY(ws_check("vit", ws, ws_bytes, p.total + part_bytes));
     // a layer GEMM: slime_gemm_ex, or the split pair where the caller asked for one (the probe brackets the GEMM as a whole)
     auto layer_gemm = [&](const slime_gemm_args& a, int splits) {
@@ -218,7 +249,7 @@ static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, i
     };
     const slime_vit_ksplit k1{1, 1, 1, 1};
     const slime_vit_ksplit& sp = ks ? *ks : k1;
-    const int g = d->image / d->patch, P = g * g, S = P + 1, D = d->hidden, F = d->inter;
+    const int S = vit_seq(d, form.plain), P = form.plain ? S : S - 1, D = d->hidden, F = d->inter;
     const int M = n * S;
     char* w = (char*)ws;
     void* xn = w + p.xn;
@@ -233,8 +264,13 @@ static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, i
 
     // patch embed (MFMA conv), class token, position table, pre-LayerNorm and the first folded LN1's operand + partial sums: ONE launch
     // (no fp32 rows: h = NULL)
-    TRY(slime_patch_embed_prenorm(pixels, pix_dtype, d->patch_w_frag, d->cls, d->pos, d->pre_ln_w, d->pre_ln_b, d->eps, nullptr, xn, lo,
-                                  stats, dt, n, d->image, d->patch, d->kpad, D, stream));
+    // -- or, in the plain form, patch embed + position table alone (slime_patch_embed_plain: S = P rows per crop)
+    if (form.plain)
+        TRY(slime_patch_embed_plain(pixels, pix_dtype, d->patch_w_frag, d->pos, nullptr, xn, lo, stats, dt, n, d->image, d->patch, d->kpad, D,
+                                    stream));
+    else
+        TRY(slime_patch_embed_prenorm(pixels, pix_dtype, d->patch_w_frag, d->cls, d->pos, d->pre_ln_w, d->pre_ln_b, d->eps, nullptr, xn, lo,
+                                      stats, dt, n, d->image, d->patch, d->kpad, D, stream));
     // hidden_states[i] of HF's output_hidden_states=True (entry 0 = the pre-LayerNorm'd embeddings, entry i = after layer i):
     // the residual stream joined to fp32 on the call's stream (capturable), one per state
     auto snapshot = [&](int idx) { return slime_gather_rows_split(xn, lo, dt, S, 0, states + (size_t)idx * M * D, SLIME_F32, n, S, D, stream); };
@@ -271,11 +307,11 @@ static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, i
         resid_update(ga);
         ga.B_frag = layer_w(d->w_o_frag, (size_t)D * D);
         PROBED(3, layer_gemm(ga, sp.out_proj));
-        // ff = act(LN2(h) W1^T + b), act = quick_gelu or the erf GELU of the OpenCLIP towers  (HF :379-380, :346-350)
+        // ff = act(LN2(h) W1^T + b), act = quick_gelu, the erf GELU of the OpenCLIP towers or the tanh GELU of the SigLIP towers  (HF :379-380, :346-350)
         ga = slime_gemm_args{};
         ga.M = M; ga.dtype = dt; ga.ln_eps = d->eps;
         ga.A = xn; ga.lda = D; ga.B = layer_w(d->w_fc1, (size_t)F * D); ga.bias = d->b_fc1 + (size_t)l * F; ga.C = ff; ga.ldc = F; ga.N = F; ga.K = D;
-        ga.epilogue = act == SLIME_ACT_GELU ? SLIME_EPI_BIAS_GELU_T : SLIME_EPI_BIAS_QUICKGELU_T; ga.ln_stats = stats; ga.ln_groups = G; ga.ln_colsum = d->colsum_fc1 + (size_t)l * F;
+        ga.epilogue = form.fc1_epilogue; ga.ln_stats = stats; ga.ln_groups = G; ga.ln_colsum = d->colsum_fc1 + (size_t)l * F;
         ga.B_frag = layer_w(d->w_fc1_frag, (size_t)F * D);
         PROBED(5, layer_gemm(ga, sp.fc1));
         // h += ff W2^T + b; prepares the next layer's LN1  (HF :381-383)
@@ -289,8 +325,10 @@ static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, i
     }
     if (hidden_f32) TRY(slime_gather_rows_split(xn, lo, dt, S, 0, hidden_f32, SLIME_F32, n, S, D, stream));
     if (out) {
-        // feature_select: 'patch' drops the class token (clip_encoder.py:38-39), cast to out dtype (:52,56)
-        TRY(slime_gather_rows_split(xn, lo, dt, S, keep_cls ? 0 : 1, out, out_dtype, n, keep_cls ? S : P, D, stream));
+        // feature_select: 'patch' drops the class token (clip_encoder.py:38-39), cast to out dtype (:52,56); the plain form has none:
+        // all S = P rows
+        const bool all_rows = keep_cls || form.plain;
+        TRY(slime_gather_rows_split(xn, lo, dt, S, all_rows ? 0 : 1, out, out_dtype, n, all_rows ? S : P, D, stream));
     }
     return SLIME_OK;
 }

@@ -32,7 +32,7 @@
 //   gemm_diag.inc (diagnostic build only): gemm_ppp_kernel, gemm_pp32b_kernel -- persistent / 32x32x16-MFMA ping-pong variants kept
 //                    as measured alternatives -- with every tuning / ablation hook and the dispatch of the forced tiles
 //
-// Epilogues: bias -> T; bias+quick-GELU -> T; bias+erf-GELU -> T; bias -> fp32; fp32 += (residual) [+ T copy and LayerNorm partial
+// Epilogues: bias -> T; bias+quick-GELU -> T; bias+erf-GELU -> T; bias+tanh-GELU -> T; bias -> fp32; fp32 += (residual) [+ T copy and LayerNorm partial
 // sums]; T(acc + bias + T residual).
 #include "gemm_shared.h"
 
@@ -88,6 +88,15 @@ __device__ __forceinline__ float gelu_erf(float x) {
     return 0.5f * x * one_plus_erf;
 }
 
+// tanh-form GELU 0.5 x (1 + tanh(c (x + 0.044715 x^3))), c = sqrt(2 / pi) (F.gelu(approximate='tanh'), HF "gelu_pytorch_tanh": the
+// SigLIP towers), written as x sigmoid(2 c (x + 0.044715 x^3)) -- the same function (1 + tanh(u) = 2 sigmoid(2u)) with the cost shape
+// of the quick-GELU: one v_exp and one v_rcp.  For x -> -inf the exponential overflows to +inf and the quotient is 0: y = -0.
+__device__ __forceinline__ float gelu_tanh(float x) {
+    constexpr float C = -2.0f * 0.79788456080286535588f * 1.4426950408889634f;     // e^(-2 c u) = 2^(C u)
+    const float u = x * fmaf(0.044715f, x * x, 1.0f);
+    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(C * u));
+}
+
 // The static operand staged from its FRAGMENT-ORDER image alone (round 5: B = NULL, no row-major copy of a packed weight).  One
 // fragment (64-column tile t, k-step s, fragment f) is 1 KiB contiguous in the image: 64 lanes x 16 B, lane = 16 lq + c for the 16
 // weight rows c of MFMA block 4 t + f and the four 8-wide k groups lq of the k-step.  An LDS-DMA piece writes 64 lanes x 16 B
@@ -102,7 +111,7 @@ __device__ __forceinline__ unsigned frag_piece_offset(const int blk, const int k
     return (((unsigned)(blk >> 2) * (unsigned)(K >> 5) + (unsigned)ks) * 4u + (unsigned)(blk & 3)) * 1024u;
 }
 
-template <int EPI> struct EpiOutIsT { static constexpr bool value = (EPI <= SLIME_EPI_BIAS_GELU_T || EPI == SLIME_EPI_BIAS_RESID_T); };
+template <int EPI> struct EpiOutIsT { static constexpr bool value = (EPI <= SLIME_EPI_BIAS_GELU_T || EPI == SLIME_EPI_BIAS_RESID_T || EPI == SLIME_EPI_BIAS_GELU_TANH_T); };
 
 // Wave-level epilogue.  A lane owns, for every 16-row step i and column-tile pair p, 8 consecutive
 // columns starting at col_base + 32 p of row row_base + 16 i.
@@ -138,7 +147,7 @@ __device__ __forceinline__ void epilogue_wave(const GemmArgs& g, f32x4 (&acc)[MI
     }
     auto in_range = [&](int row) { return FULL || row < g.M; };
     if constexpr (LN) {
-        // LayerNorm-fold epilogues (BIAS_T / BIAS_QUICKGELU_T / BIAS_GELU_T): pre-activation = rstd[m] * (acc - mu[m] * colsum[n]) + bias[n],
+        // LayerNorm-fold epilogues (BIAS_T / BIAS_QUICKGELU_T / BIAS_GELU_T / BIAS_GELU_TANH_T): pre-activation = rstd[m] * (acc - mu[m] * colsum[n]) + bias[n],
         // evaluated as fma(rstd, acc, fma(-mu rstd, colsum, bias)).  Everything that is loaded (bias, colsum, the row table) is
         // fetched up front; each 8-column group is then read from the accumulators, finished and stored at once, so only 8
         // results are live at a time (the in-place form below keeps all of them in VGPRs, which spills next to 64 constants).
@@ -185,6 +194,10 @@ __device__ __forceinline__ void epilogue_wave(const GemmArgs& g, f32x4 (&acc)[MI
                     // epilogue below, element by element; the group is stored before the next one is formed
 #pragma unroll
                     for (int j = 0; j < 8; ++j) v[j] = gelu_erf(v[j]);
+                } else if constexpr (EPI == SLIME_EPI_BIAS_GELU_TANH_T) {
+                    // tanh GELU of the folded pre-activation (towers with hidden_act 'gelu_pytorch_tanh'), element by element
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] = gelu_tanh(v[j]);
                 }
                 const u32x4 w = pack8<T>(v);
                 if (in_range(row))
@@ -387,6 +400,9 @@ __device__ __forceinline__ void epilogue_wave(const GemmArgs& g, f32x4 (&acc)[MI
                     } else if constexpr (EPI == SLIME_EPI_BIAS_GELU_T) {        // erf GELU (nn.GELU())
                         a = gelu_erf(a);
                         b = gelu_erf(b);
+                    } else if constexpr (EPI == SLIME_EPI_BIAS_GELU_TANH_T) {   // tanh GELU (F.gelu(approximate='tanh'))
+                        a = gelu_tanh(a);
+                        b = gelu_tanh(b);
                     }
                     acc[i][2 * p][j] = a; acc[i][2 * p + 1][j] = b;
                 }
@@ -472,7 +488,8 @@ __device__ __forceinline__ void epilogue_mix(const GemmArgs& g, f32x4 (&acc)[8][
 template <typename T, int EPI, int MI, int NI>
 __device__ __forceinline__ void run_epilogue(const GemmArgs& g, f32x4 (&acc)[MI][NI], const int row_base, const int col_base,
                                              const bool full, const float* lnrow_lane) {
-    constexpr bool CAN_LN = (EPI == SLIME_EPI_BIAS_T || EPI == SLIME_EPI_BIAS_QUICKGELU_T || EPI == SLIME_EPI_BIAS_GELU_T);
+    constexpr bool CAN_LN = (EPI == SLIME_EPI_BIAS_T || EPI == SLIME_EPI_BIAS_QUICKGELU_T || EPI == SLIME_EPI_BIAS_GELU_T ||
+                             EPI == SLIME_EPI_BIAS_GELU_TANH_T);
     if constexpr (CAN_LN) {
         if (g.ln_stats) {
             if (full) epilogue_wave<T, EPI, MI, NI, true, true>(g, acc, row_base, col_base, lnrow_lane);
@@ -1496,6 +1513,7 @@ static int launch_T(const GemmArgs& g, int epi, hipStream_t stream) {
         case SLIME_EPI_BIAS_RESID_T: return launch_epi<T, SLIME_EPI_BIAS_RESID_T>(g, stream);
         case SLIME_EPI_BIAS_GELU_MIX_T: return launch_db<T, SLIME_EPI_BIAS_GELU_MIX_T, 8>(g, stream);    // direct-B only (checked by slime_gemm_ex)
         case SLIME_EPI_BIAS_RESID_SPLIT_LN: return launch_epi<T, SLIME_EPI_BIAS_RESID_SPLIT_LN>(g, stream);
+        case SLIME_EPI_BIAS_GELU_TANH_T: return launch_epi<T, SLIME_EPI_BIAS_GELU_TANH_T>(g, stream);
     }
     slime_set_error("gemm: unknown epilogue %d", epi);
     return SLIME_EINVAL;
@@ -1533,8 +1551,9 @@ static int gemm_check_args(const slime_gemm_args* a, GemmArgs& out) {
     SLIME_REQUIRE(((uintptr_t)a->A % 16 == 0) && ((uintptr_t)a->B % 16 == 0) && ((uintptr_t)a->C % 16 == 0) &&
                   (!a->bias || (uintptr_t)a->bias % 16 == 0), "gemm: pointers must be 16-byte aligned");
     if (a->ln_stats) {
-        SLIME_REQUIRE(a->epilogue == SLIME_EPI_BIAS_T || a->epilogue == SLIME_EPI_BIAS_QUICKGELU_T || a->epilogue == SLIME_EPI_BIAS_GELU_T,
-                      "gemm: the LayerNorm fold is built for the BIAS_T / BIAS_QUICKGELU_T / BIAS_GELU_T epilogues");
+        SLIME_REQUIRE(a->epilogue == SLIME_EPI_BIAS_T || a->epilogue == SLIME_EPI_BIAS_QUICKGELU_T || a->epilogue == SLIME_EPI_BIAS_GELU_T ||
+                      a->epilogue == SLIME_EPI_BIAS_GELU_TANH_T,
+                      "gemm: the LayerNorm fold is built for the BIAS_T / BIAS_QUICKGELU_T / BIAS_GELU_T / BIAS_GELU_TANH_T epilogues");
         SLIME_REQUIRE(a->ln_colsum && a->ln_groups > 0 && ((uintptr_t)a->ln_colsum % 16) == 0 && ((uintptr_t)a->ln_stats % 16) == 0,
                       "gemm: LayerNorm fold needs ln_colsum [N] and ln_groups partial sums per row (16-byte aligned)");
         SLIME_REQUIRE(a->ln_groups * 64 == K, "gemm: LayerNorm fold: ln_groups=%d partial sums of 64 columns must cover K=%d", a->ln_groups, K);
@@ -1545,8 +1564,8 @@ static int gemm_check_args(const slime_gemm_args* a, GemmArgs& out) {
     if (a->row_map)
         SLIME_REQUIRE(!a->ln_stats && ((uintptr_t)a->row_map % 4) == 0 &&
                       (a->epilogue == SLIME_EPI_BIAS_T || a->epilogue == SLIME_EPI_BIAS_QUICKGELU_T || a->epilogue == SLIME_EPI_BIAS_GELU_T ||
-                       a->epilogue == SLIME_EPI_BIAS_F32),
-                      "gemm: row_map goes with the plain T / fp32 epilogues (BIAS_T, BIAS_QUICKGELU_T, BIAS_GELU_T, BIAS_F32; no LayerNorm fold)");
+                       a->epilogue == SLIME_EPI_BIAS_F32 || a->epilogue == SLIME_EPI_BIAS_GELU_TANH_T),
+                      "gemm: row_map goes with the plain T / fp32 epilogues (BIAS_T, BIAS_QUICKGELU_T, BIAS_GELU_T, BIAS_GELU_TANH_T, BIAS_F32; no LayerNorm fold)");
     if (a->epilogue == SLIME_EPI_BIAS_RESID_SPLIT_LN)
         SLIME_REQUIRE(a->lo8 && a->stats_out && a->ldlo >= N && a->ldlo % 8 == 0 && ((uintptr_t)a->lo8 % 8) == 0 &&
                       ((uintptr_t)a->stats_out % 8) == 0 && N % 64 == 0 && a->lo8 != a->C,

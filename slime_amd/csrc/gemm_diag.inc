@@ -307,6 +307,7 @@ __device__ __forceinline__ void epilogue_wave32(const GemmArgs& g, f32x16 (&acc)
                     float a = acc[mi][nj][r] + bias[nj][r];
                     if constexpr (EPI == SLIME_EPI_BIAS_QUICKGELU_T) a = a * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * a));
                     else if constexpr (EPI == SLIME_EPI_BIAS_GELU_T) a = gelu_erf(a);
+                    else if constexpr (EPI == SLIME_EPI_BIAS_GELU_TANH_T) a = gelu_tanh(a);
                     acc[mi][nj][r] = a;
                 }
         if constexpr (EpiOutIsT<EPI>::value) {

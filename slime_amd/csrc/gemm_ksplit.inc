@@ -226,7 +226,7 @@ static int launch_ksplit_tile(const GemmArgs& g, int epi, char* ws, int splits, 
 #define KSPLIT_EPI(E) case E: return launch_ksplit_reduce<T, BM, BN, WAVES_M, WAVES_N, E>(g, ws, splits, stream);
         KSPLIT_EPI(SLIME_EPI_BIAS_T) KSPLIT_EPI(SLIME_EPI_BIAS_QUICKGELU_T) KSPLIT_EPI(SLIME_EPI_BIAS_GELU_T) KSPLIT_EPI(SLIME_EPI_BIAS_F32)
         KSPLIT_EPI(SLIME_EPI_BIAS_RESID_F32) KSPLIT_EPI(SLIME_EPI_BIAS_RESID_F32_LN) KSPLIT_EPI(SLIME_EPI_BIAS_RESID_T)
-        KSPLIT_EPI(SLIME_EPI_BIAS_RESID_SPLIT_LN)
+        KSPLIT_EPI(SLIME_EPI_BIAS_RESID_SPLIT_LN) KSPLIT_EPI(SLIME_EPI_BIAS_GELU_TANH_T)
 #undef KSPLIT_EPI
     }
     return SLIME_EINVAL;                                  // unreachable: slime_gemm_ksplit checked the epilogue before the first launch
@@ -257,7 +257,7 @@ extern "C" int slime_gemm_ksplit(const slime_gemm_args* a, int splits, void* ws,
                   splits, a->K / 64);
     SLIME_REQUIRE(a->epilogue != SLIME_EPI_BIAS_GELU_MIX_T, "gemm_ksplit: BIAS_GELU_MIX_T runs on the direct-B kernel only; the split is built "
                                                              "for the LDS-staged kernel");
-    SLIME_REQUIRE(a->epilogue >= SLIME_EPI_BIAS_T && a->epilogue <= SLIME_EPI_BIAS_RESID_SPLIT_LN, "gemm: unknown epilogue %d", a->epilogue);
+    SLIME_REQUIRE(a->epilogue >= SLIME_EPI_BIAS_T && a->epilogue <= SLIME_EPI_BIAS_GELU_TANH_T, "gemm: unknown epilogue %d", a->epilogue);
     SLIME_REQUIRE(a->dtype == SLIME_BF16 || a->dtype == SLIME_F16, "gemm: dtype %d is not a 16-bit MFMA type", a->dtype);
     const size_t need = slime_gemm_ksplit_workspace_bytes(a->M, a->N, splits);
     SLIME_REQUIRE(need < (1ull << 32), "gemm_ksplit: %zu B of partial products (splits=%d x %d padded rows x N=%d fp32) reach the 4 GiB the "

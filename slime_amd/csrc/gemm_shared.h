@@ -9,7 +9,7 @@ struct GemmArgs {
     int lda, ldc, M, N, K;
     int group_m;      // row tiles per L2 patch of the GROUP_M walks (0 = the kernel's default)
     unsigned long long* dbg;   // ABL & 8 builds only: 4 s_memtime stamps per workgroup
-    // LayerNorm folded into this GEMM (consumer side; epilogues BIAS_T / BIAS_QUICKGELU_T / BIAS_GELU_T): A holds the UN-normalised 16-bit rows x,
+    // LayerNorm folded into this GEMM (consumer side; epilogues BIAS_T / BIAS_QUICKGELU_T / BIAS_GELU_T / BIAS_GELU_TANH_T): A holds the UN-normalised 16-bit rows x,
     // B = W . diag(gamma), bias = b + W beta, and the epilogue applies  rstd * (acc - mu * colsum[n]) + bias[n]  with the row
     // statistics (mu, rstd) finalised per workgroup from the producer's per-64-column partial sums.  NULL = plain GEMM.
     const float* ln_stats; int ln_groups; const float* ln_colsum; float ln_eps;

@@ -21,6 +21,10 @@
 //      the layer stack wants: the fp32 residual rows (or their split form: T(h) + one byte), T(h) and its per-64-column partial sums
 //      (the first folded LayerNorm of slime_gemm_ex).  Row 0 of every crop (class token + position 0) is input independent; the
 //      workgroup that owns a crop's first patch rows writes it.
+//
+// The SigLIP towers (no class token, no pre-LayerNorm, a conv bias) run the second compile-time form of the same body, steps 1-3
+// shared:  h[n, P, D] = conv16x16/16(pixels) + pos'[P, D]  (HF SiglipVisionEmbeddings.forward; pos' = position_embedding +
+// patch_embedding.bias, added at pack time), slime_patch_embed_plain.
 #include "gemm_shared.h"
 
 namespace {
@@ -90,8 +94,12 @@ __device__ __forceinline__ void pe_cls_row(const PEArgs& a, const long grow, con
     }
 }
 
-template <typename T, typename PixT, int D, int NW>
-__global__ void __launch_bounds__(NW * 64) patch_embed_kernel(PEArgs a) {
+// The front end's two compile-time forms share staging, re-tiling and the MFMA loop:
+//   PLAIN = false  the CLIP form above (class row, + position row, pre-LayerNorm);
+//   PLAIN = true   h[n, P, D] = conv(pixels) + pos'[P, D], pos' = position_embedding + conv bias (added at pack time): no class row
+//                  (output row = patch index, nothing writes a row 0), no LayerNorm (no mean / rstd, no affine) -- the SigLIP towers.
+template <typename T, typename PixT, int D, int NW, bool PLAIN>
+__device__ __forceinline__ void pe_body(const PEArgs& a) {
     constexpr int CW = D / NW, NT = CW / 64, NF = CW / 16, NP = NF / 2, NTHR = NW * 64;
     static_assert(CW % 64 == 0, "a wave owns whole 64-column groups (LayerNorm partial sums are wave local)");
     extern __shared__ __attribute__((aligned(16))) char smem_pe[];
@@ -226,8 +234,8 @@ __global__ void __launch_bounds__(NW * 64) patch_embed_kernel(PEArgs a) {
     for (int mi = 0; mi < PE_MT; ++mi) {
         const int r = 16 * mi + li;
         ok[mi] = r < rows_valid;
-        const int t = 1 + prow0 * g + min(r, rows_valid - 1);         // token index (clamped: masked rows compute on a valid row's table)
-        grow[mi] = (long)crop * (P + 1) + t;
+        const int t = (PLAIN ? 0 : 1) + prow0 * g + min(r, rows_valid - 1);   // token index (clamped: masked rows compute on a valid row's table)
+        grow[mi] = (long)crop * (P + (PLAIN ? 0 : 1)) + t;
         const float* pr = a.pos + (size_t)t * D + cw0 + 8 * lg;
         float s = 0.f;
 #pragma unroll
@@ -238,7 +246,7 @@ __global__ void __launch_bounds__(NW * 64) patch_embed_kernel(PEArgs a) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) { s += acc[mi][2 * p][k]; s += acc[mi][2 * p + 1][k]; }
         }
-        part[mi] = pe_rows4_allsum(s);
+        if constexpr (!PLAIN) part[mi] = pe_rows4_allsum(s);
     }
     auto all_waves = [&](float (&v)[PE_MT]) {                        // v[mi] (this wave's share of row 16 mi + li) -> sum over the waves
         __syncthreads();                                              // the previous round's reads are done
@@ -255,31 +263,34 @@ __global__ void __launch_bounds__(NW * 64) patch_embed_kernel(PEArgs a) {
             v[mi] = s;
         }
     };
-    all_waves(part);
     float mean[PE_MT];
-#pragma unroll
-    for (int mi = 0; mi < PE_MT; ++mi) {
-        mean[mi] = part[mi] * (1.0f / D);
-        float q = 0.f;
-#pragma unroll
-        for (int f = 0; f < NF; ++f)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { const float d = __fsub_rn(acc[mi][f][k], mean[mi]); q = __fmaf_rn(d, d, q); }
-        part[mi] = pe_rows4_allsum(q);
-    }
-    all_waves(part);
     float gw[NP][8], gb[NP][8];
+    if constexpr (!PLAIN) {
+        all_waves(part);
 #pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const int c = cw0 + 32 * p + 8 * lg;
-        const float4 w0 = *reinterpret_cast<const float4*>(a.ln_w + c), w1 = *reinterpret_cast<const float4*>(a.ln_w + c + 4);
-        const float4 b0 = *reinterpret_cast<const float4*>(a.ln_b + c), b1 = *reinterpret_cast<const float4*>(a.ln_b + c + 4);
-        gw[p][0] = w0.x; gw[p][1] = w0.y; gw[p][2] = w0.z; gw[p][3] = w0.w; gw[p][4] = w1.x; gw[p][5] = w1.y; gw[p][6] = w1.z; gw[p][7] = w1.w;
-        gb[p][0] = b0.x; gb[p][1] = b0.y; gb[p][2] = b0.z; gb[p][3] = b0.w; gb[p][4] = b1.x; gb[p][5] = b1.y; gb[p][6] = b1.z; gb[p][7] = b1.w;
+        for (int mi = 0; mi < PE_MT; ++mi) {
+            mean[mi] = part[mi] * (1.0f / D);
+            float q = 0.f;
+#pragma unroll
+            for (int f = 0; f < NF; ++f)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { const float d = __fsub_rn(acc[mi][f][k], mean[mi]); q = __fmaf_rn(d, d, q); }
+            part[mi] = pe_rows4_allsum(q);
+        }
+        all_waves(part);
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const int c = cw0 + 32 * p + 8 * lg;
+            const float4 w0 = *reinterpret_cast<const float4*>(a.ln_w + c), w1 = *reinterpret_cast<const float4*>(a.ln_w + c + 4);
+            const float4 b0 = *reinterpret_cast<const float4*>(a.ln_b + c), b1 = *reinterpret_cast<const float4*>(a.ln_b + c + 4);
+            gw[p][0] = w0.x; gw[p][1] = w0.y; gw[p][2] = w0.z; gw[p][3] = w0.w; gw[p][4] = w1.x; gw[p][5] = w1.y; gw[p][6] = w1.z; gw[p][7] = w1.w;
+            gb[p][0] = b0.x; gb[p][1] = b0.y; gb[p][2] = b0.z; gb[p][3] = b0.w; gb[p][4] = b1.x; gb[p][5] = b1.y; gb[p][6] = b1.z; gb[p][7] = b1.w;
+        }
     }
 #pragma unroll
     for (int mi = 0; mi < PE_MT; ++mi) {
-        const float rstd = rsqrtf(__fmaf_rn(part[mi], 1.0f / D, a.eps));       // (operations written out: no contraction left to the compiler)
+        float rstd = 0.f;
+        if constexpr (!PLAIN) rstd = rsqrtf(__fmaf_rn(part[mi], 1.0f / D, a.eps));       // (operations written out: no contraction left to the compiler)
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             float sx = 0.f, sq = 0.f;
@@ -288,7 +299,10 @@ __global__ void __launch_bounds__(NW * 64) patch_embed_kernel(PEArgs a) {
                 const int p = 2 * t + h2;
                 float y[8];
 #pragma unroll
-                for (int e = 0; e < 8; ++e) y[e] = __fmaf_rn(__fmul_rn(__fsub_rn(acc[mi][2 * p + (e >> 2)][e & 3], mean[mi]), rstd), gw[p][e], gb[p][e]);
+                for (int e = 0; e < 8; ++e) {
+                    if constexpr (PLAIN) y[e] = acc[mi][2 * p + (e >> 2)][e & 3];
+                    else y[e] = __fmaf_rn(__fmul_rn(__fsub_rn(acc[mi][2 * p + (e >> 2)][e & 3], mean[mi]), rstd), gw[p][e], gb[p][e]);
+                }
                 const size_t off = (size_t)grow[mi] * D + cw0 + 32 * p + 8 * lg;
                 const u32x4 w = pack8<T>(y);
                 float r[8];
@@ -318,25 +332,38 @@ __global__ void __launch_bounds__(NW * 64) patch_embed_kernel(PEArgs a) {
         }
     }
     // the crop's class-token row (token 0): input independent, written by the workgroup that owns the first patch rows
-    if (pair == 0 && wave == 0) pe_cls_row<T, D>(a, (long)crop * (P + 1), lane);
+    if constexpr (!PLAIN) { if (pair == 0 && wave == 0) pe_cls_row<T, D>(a, (long)crop * (P + 1), lane); }
 }
 
 template <typename T, typename PixT, int D, int NW>
+__global__ void __launch_bounds__(NW * 64) patch_embed_kernel(PEArgs a) { pe_body<T, PixT, D, NW, false>(a); }
+
+template <typename T, typename PixT, int D, int NW>
+__global__ void __launch_bounds__(NW * 64) patch_embed_plain_kernel(PEArgs a) { pe_body<T, PixT, D, NW, true>(a); }
+
+template <typename T, typename PixT, int D, int NW, bool PLAIN>
 int launch_pe(const PEArgs& a, size_t lds, hipStream_t s) {
-    auto kern = patch_embed_kernel<T, PixT, D, NW>;
-    SLIME_SET_LDS_ONCE(kern, 160 * 1024, "patch_embed");       // the geometry (image, patch, kpad) is a run-time argument: opt in to the maximum
-    hipLaunchKernelGGL(kern, dim3((unsigned)(a.n * ((a.g + 1) / 2))), dim3(NW * 64), lds, s, a);
+    const dim3 grid((unsigned)(a.n * ((a.g + 1) / 2))), block(NW * 64);
+    if constexpr (PLAIN) {
+        auto kern = patch_embed_plain_kernel<T, PixT, D, NW>;
+        SLIME_SET_LDS_ONCE(kern, 160 * 1024, "patch_embed_plain");
+        hipLaunchKernelGGL(kern, grid, block, lds, s, a);
+    } else {
+        auto kern = patch_embed_kernel<T, PixT, D, NW>;
+        SLIME_SET_LDS_ONCE(kern, 160 * 1024, "patch_embed");       // the geometry (image, patch, kpad) is a run-time argument: opt in to the maximum
+        hipLaunchKernelGGL(kern, grid, block, lds, s, a);
+    }
     SLIME_CHECK_LAUNCH("patch_embed");
     return SLIME_OK;
 }
 
-template <typename T, typename PixT>
+template <typename T, typename PixT, bool PLAIN>
 int launch_pe_d(const PEArgs& a, int D, size_t lds, hipStream_t s) {
     switch (D) {
-        case 128: return launch_pe<T, PixT, 128, 2>(a, lds, s);
-        case 256: return launch_pe<T, PixT, 256, 4>(a, lds, s);
-        case 768: return launch_pe<T, PixT, 768, 6>(a, lds, s);        // six waves of 128 columns, as at 1024 (ViT-B widths)
-        case 1024: return launch_pe<T, PixT, 1024, 8>(a, lds, s);
+        case 128: return launch_pe<T, PixT, 128, 2, PLAIN>(a, lds, s);
+        case 256: return launch_pe<T, PixT, 256, 4, PLAIN>(a, lds, s);
+        case 768: return launch_pe<T, PixT, 768, 6, PLAIN>(a, lds, s);        // six waves of 128 columns, as at 1024 (ViT-B widths)
+        case 1024: return launch_pe<T, PixT, 1024, 8, PLAIN>(a, lds, s);
     }
     slime_set_error("patch_embed: D=%d unsupported (128, 256, 768, 1024)", D);
     return SLIME_EINVAL;
@@ -365,10 +392,11 @@ int slime_patch_embed_geometry(int image, int patch, int kpad, int D, size_t* ld
     return SLIME_OK;
 }
 
-extern "C" int slime_patch_embed_prenorm(const void* pixels, int pix_dtype, const void* patch_w_frag, const float* cls, const float* pos,
-                                         const float* ln_w, const float* ln_b, float eps, float* h, void* x16, void* lo8, float* stats,
-                                         int dtype, int n, int image, int patch, int kpad, int D, void* stream) {
-    SLIME_REQUIRE(pixels && patch_w_frag && cls && pos && ln_w && ln_b && n > 0, "patch_embed: bad input");
+// The one host body behind both entries: argument checks, geometry, launch.  plain: no class token, no pre-LayerNorm (cls / ln_w / ln_b unused).
+static int pe_run(bool plain, const void* pixels, int pix_dtype, const void* patch_w_frag, const float* cls, const float* pos,
+                  const float* ln_w, const float* ln_b, float eps, float* h, void* x16, void* lo8, float* stats,
+                  int dtype, int n, int image, int patch, int kpad, int D, void* stream) {
+    SLIME_REQUIRE(pixels && patch_w_frag && pos && (plain || (cls && ln_w && ln_b)) && n > 0, "patch_embed: bad input");
     SLIME_REQUIRE(h || x16, "patch_embed: no output requested (h and / or x16)");
     SLIME_REQUIRE(!lo8 || x16, "patch_embed: the split residual's lower part (lo8) comes with its upper part x16");
     SLIME_REQUIRE(!stats || x16, "patch_embed: stats are the partial sums of x16");
@@ -383,7 +411,24 @@ extern "C" int slime_patch_embed_prenorm(const void* pixels, int pix_dtype, cons
                   "patch_embed: pointers must be 16-byte aligned");
     PEArgs a{pixels, (const char*)patch_w_frag, cls, pos, ln_w, ln_b, eps, h, (char*)x16, (char*)lo8, stats, n, image, patch, kpad, g};
     hipStream_t s = (hipStream_t)stream;
+    if (plain) {
+        if (dtype == SLIME_F16)
+            return pix_dtype == SLIME_F32 ? launch_pe_d<F16, float, true>(a, D, lds, s) : launch_pe_d<F16, unsigned short, true>(a, D, lds, s);
+        return pix_dtype == SLIME_F32 ? launch_pe_d<BF16, float, true>(a, D, lds, s) : launch_pe_d<BF16, unsigned short, true>(a, D, lds, s);
+    }
     if (dtype == SLIME_F16)
-        return pix_dtype == SLIME_F32 ? launch_pe_d<F16, float>(a, D, lds, s) : launch_pe_d<F16, unsigned short>(a, D, lds, s);
-    return pix_dtype == SLIME_F32 ? launch_pe_d<BF16, float>(a, D, lds, s) : launch_pe_d<BF16, unsigned short>(a, D, lds, s);
+        return pix_dtype == SLIME_F32 ? launch_pe_d<F16, float, false>(a, D, lds, s) : launch_pe_d<F16, unsigned short, false>(a, D, lds, s);
+    return pix_dtype == SLIME_F32 ? launch_pe_d<BF16, float, false>(a, D, lds, s) : launch_pe_d<BF16, unsigned short, false>(a, D, lds, s);
+}
+
+extern "C" int slime_patch_embed_prenorm(const void* pixels, int pix_dtype, const void* patch_w_frag, const float* cls, const float* pos,
+                                         const float* ln_w, const float* ln_b, float eps, float* h, void* x16, void* lo8, float* stats,
+                                         int dtype, int n, int image, int patch, int kpad, int D, void* stream) {
+    return pe_run(false, pixels, pix_dtype, patch_w_frag, cls, pos, ln_w, ln_b, eps, h, x16, lo8, stats, dtype, n, image, patch, kpad, D, stream);
+}
+
+extern "C" int slime_patch_embed_plain(const void* pixels, int pix_dtype, const void* patch_w_frag, const float* pos, float* h, void* x16,
+                                       void* lo8, float* stats, int dtype, int n, int image, int patch, int kpad, int D, void* stream) {
+    return pe_run(true, pixels, pix_dtype, patch_w_frag, nullptr, pos, nullptr, nullptr, 0.f, h, x16, lo8, stats, dtype, n, image, patch, kpad,
+                  D, stream);
 }

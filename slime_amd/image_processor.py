@@ -81,3 +81,45 @@ class ClipImageProcessor:
         return {"pixel_values": out}
 
     __call__ = preprocess
+
+
+SIGLIP_MEAN = (0.5, 0.5, 0.5)
+SIGLIP_STD = (0.5, 0.5, 0.5)
+
+
+class SiglipImageProcessor(ClipImageProcessor):
+    """The role of HF ``SiglipImageProcessor``: resize to exactly ``(size, size)`` -- the aspect ratio is NOT kept and there is no
+    centre crop -- with the resample filter of ``preprocessor_config.json``, then the rescale / normalise arithmetic of the class
+    above (bit-identical to transformers' PIL backend).  ``size`` carries ``shortest_edge`` next to ``height`` / ``width`` and
+    ``crop_size`` is the output size: the attribute surface ``mm_utils`` touches.  ``do_center_crop`` is False: the device
+    pre-processing modes that would resize the shortest edge and cut a centre window refuse this processor (mm_utils)."""
+    do_center_crop = False
+
+    def __init__(self, size: int = 384, image_mean: Sequence[float] = SIGLIP_MEAN, image_std: Sequence[float] = SIGLIP_STD,
+                 rescale_factor: float = 1 / 255, resample: int = Image.BICUBIC):
+        super().__init__(size, size, image_mean, image_std, rescale_factor)
+        self.size = {"shortest_edge": int(size), "height": int(size), "width": int(size)}
+        self.resample = Image.Resampling(int(resample))
+
+    @classmethod
+    def from_pretrained(cls, path: str, default_size: int = 384) -> "SiglipImageProcessor":
+        f = os.path.join(path, "preprocessor_config.json")
+        if not os.path.isfile(f):
+            return cls(default_size)
+        cfg = json.load(open(f))
+        size = cfg.get("size", default_size)
+        if isinstance(size, dict):
+            h, w = size.get("height", size.get("shortest_edge", default_size)), size.get("width", size.get("shortest_edge", default_size))
+            if h != w:
+                raise ValueError(f"SiglipImageProcessor: size {size} is not square (the tower takes one image_size)")
+            size = h
+        return cls(size, cfg.get("image_mean", SIGLIP_MEAN), cfg.get("image_std", SIGLIP_STD), cfg.get("rescale_factor", 1 / 255),
+                   cfg.get("resample", Image.BICUBIC))
+
+    def _resize_center_crop(self, img: Image.Image) -> np.ndarray:
+        """(the base class's hook) RGB, then ONE resize to (size, size); an image of that size already is passed through."""
+        img = img.convert("RGB")
+        s = self.crop_size["height"]
+        if img.size != (s, s):
+            img = img.resize((s, s), resample=self.resample)
+        return np.asarray(img)

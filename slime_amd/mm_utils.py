@@ -312,6 +312,16 @@ def process_images_device(images, image_processor, model_cfg, device, dtype=torc
     if not (s == crop == image_processor.crop_size["width"]):
         raise ValueError(f"process_images_device needs shortest_edge == crop height == crop width, got shortest_edge {s} and "
                          f"crop_size {image_processor.crop_size['height']}x{image_processor.crop_size['width']}; use process_images")
+    if not getattr(image_processor, "do_center_crop", True):
+        # a processor that resizes to exactly (size, size) (SiglipImageProcessor): the views of 'pad' / 'any_res' / 'pad_then_devide'
+        # are squared before their bicubic resize, which IS that processor's arithmetic; the bare mode's view job resizes the
+        # shortest edge and cuts a centre window (ClipImageProcessor), which is not
+        if mode not in ("pad", "any_res", "pad_then_devide"):
+            raise ValueError(f"process_images_device: image_aspect_ratio={mode!r} on the device is CLIP's shortest-edge resize + centre "
+                             f"crop; {type(image_processor).__name__} resizes to exactly {crop}x{crop} without a crop: use process_images")
+        if int(getattr(image_processor, "resample", Image.BICUBIC)) != int(Image.BICUBIC):
+            raise ValueError(f"process_images_device resamples bicubic; {type(image_processor).__name__} is configured with resample="
+                             f"{int(image_processor.resample)}: use process_images")
     if len(images) == 0:
         raise ValueError("process_images_device: no images")
     bg = tuple(int(x * 255) for x in image_processor.image_mean)

@@ -2,16 +2,29 @@
 import os
 
 from .clip_encoder import CLIPVisionTower, SYNTHETIC_PREFIX
+from .siglip_encoder import SigLipVisionTower, SYNTHETIC_SIGLIP_PREFIX, is_siglip_dir
+
+
+def is_siglip_tower(vision_tower: str) -> bool:
+    """A SigLIP tower is selected by an existing directory whose config.json has ``model_type`` siglip_vision_model or siglip (its
+    ``vision_config`` is used), by a hub-style name containing ``siglip`` (resolved from the local HF cache), or by the offline
+    stand-in ``synthetic-siglip:<seed>``."""
+    if os.path.exists(vision_tower):
+        return is_siglip_dir(vision_tower)
+    return vision_tower.startswith(SYNTHETIC_SIGLIP_PREFIX) or "siglip" in vision_tower.lower()
 
 
 def build_vision_tower(vision_tower_cfg, **kwargs):
     """Reads ``mm_vision_tower`` (else ``vision_tower``) from the config; accepts an existing path,
     hub-style names starting with ``openai`` / ``laion`` or containing ``ShareGPT4V`` (resolved from the
-    local HF cache: there is no network here), plus the offline stand-in ``synthetic:<seed>``.
+    local HF cache: there is no network here), plus the offline stand-in ``synthetic:<seed>``; SigLIP towers
+    (:func:`is_siglip_tower`) go to ``SigLipVisionTower``.
     Anything else raises ``ValueError('Unknown vision tower: ...')`` like the reference."""
     vision_tower = getattr(vision_tower_cfg, "mm_vision_tower", getattr(vision_tower_cfg, "vision_tower", None))
     if vision_tower is None:
         raise ValueError("Unknown vision tower: None")
+    if is_siglip_tower(vision_tower):
+        return SigLipVisionTower(vision_tower, args=vision_tower_cfg, **kwargs)
     if (os.path.exists(vision_tower) or vision_tower.startswith("openai") or vision_tower.startswith("laion")
             or "ShareGPT4V" in vision_tower or vision_tower.startswith(SYNTHETIC_PREFIX)):
         return CLIPVisionTower(vision_tower, args=vision_tower_cfg, **kwargs)

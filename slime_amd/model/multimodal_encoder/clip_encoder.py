@@ -72,15 +72,17 @@ class _VisionTransformer(nn.Module):
         self.post_layernorm = nn.LayerNorm(c.hidden_size, eps=c.layer_norm_eps)
 
 
-class HipCLIPVisionModel(nn.Module):
-    """Parameter container with HF ``CLIPVisionModel`` state-dict keys (transformers-4.37 names,
-    ``vision_model.`` prefix; prefix-free 5.x keys are accepted on load) whose forward is the HIP
-    tower.  The torch sub-modules are never called: they only give the parameters their names."""
+class HipVisionModelBase(nn.Module):
+    """What the HIP tower models share (CLIP layout: HipCLIPVisionModel; SigLIP layout: siglip_encoder.HipSiglipVisionModel): the
+    parameter container's key handling, the packed-weight cache with one workspace per stream slot, the two-stream split of
+    ``encode`` and the ``k_split`` setting.  A subclass builds ``self.vision_model`` (the torch sub-modules are never called: they
+    only give the parameters their names) and says how its tower is packed and run."""
+    TOP_LEVEL = ()            # first key components under ``vision_model.`` (a prefix-free 5.x key is recognised by them)
+    DROPPED = ()              # key prefixes under ``vision_model.`` a checkpoint may carry and the tower never runs
 
-    def __init__(self, config: VisionConfig, compute_dtype: torch.dtype = torch.bfloat16):
+    def __init__(self, config, compute_dtype: torch.dtype = torch.bfloat16):
         super().__init__()
         self.config = config
-        self.vision_model = _VisionTransformer(config)
         self.compute_dtype = compute_dtype     # MFMA operand type used when the parameters are fp32
         self.two_streams = True
         # crop count from which encode() splits the batch over two streams: 8 is the measured break-even of ViT-L/14-336 on MI355X
@@ -93,15 +95,34 @@ class HipCLIPVisionModel(nn.Module):
         self.k_split = None
         self._packed: Dict = {}
         self._streams: Optional[List[torch.cuda.Stream]] = None
-        self.requires_grad_(False)
+
+    # -- what a layout provides ---------------------------------------------------------------
+    def _anchor(self) -> torch.Tensor:
+        """A parameter every tower of the layout has: its dtype / device are the model's."""
+        raise NotImplementedError
+
+    def _pack(self, select_layer: int):
+        raise NotImplementedError
+
+    def _share(self, base):
+        """A second packed object over ``base``'s weights with a workspace of its own (the second stream's slot)."""
+        raise NotImplementedError
+
+    def _run(self, pt, pixel_values, out_dtype, keep_cls: bool, **kw):
+        raise NotImplementedError
+
+    def _rows(self, keep_cls: bool) -> int:
+        raise NotImplementedError
 
     # -- state dict: accept both HF key generations -------------------------------------------
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         for k in [k for k in state_dict if k.startswith(prefix)]:
             tail = k[len(prefix):]
             canon = "vision_model." + canonical_tower_key(tail)
-            if tail != canon and canon.split(".")[1] in ("embeddings", "pre_layrnorm", "encoder", "post_layernorm"):
+            if tail != canon and canon.split(".")[1] in self.TOP_LEVEL:
                 state_dict[prefix + canon] = state_dict.pop(k)
+        for k in [k for k in state_dict if any(k.startswith(prefix + "vision_model." + d) for d in self.DROPPED)]:
+            state_dict.pop(k)
         for k in [k for k in state_dict if k.endswith("embeddings.position_ids")]:
             state_dict.pop(k)                      # HF buffer, pure arange
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
@@ -113,24 +134,23 @@ class HipCLIPVisionModel(nn.Module):
 
     @property
     def dtype(self) -> torch.dtype:
-        return self.vision_model.embeddings.class_embedding.dtype
+        return self._anchor().dtype
 
     @property
     def device(self) -> torch.device:
-        return self.vision_model.embeddings.class_embedding.device
+        return self._anchor().device
 
     def operand_dtype(self) -> torch.dtype:
         return self.dtype if self.dtype in (torch.bfloat16, torch.float16) else self.compute_dtype
 
-    def packed(self, select_layer: int, slot: int = 0) -> ops.PackedTower:
+    def packed(self, select_layer: int, slot: int = 0):
         key = (select_layer, self.operand_dtype(), str(self.device), slot)
         if key not in self._packed:
             base = self._packed.get((select_layer, self.operand_dtype(), str(self.device), 0))
             if base is not None:                   # extra slots share the weights, own a workspace
-                self._packed[key] = ops.PackedTower(base.cfg, base.dtype, base.layers_run, base.tensors, base.desc, act=base.act)
+                self._packed[key] = self._share(base)
             else:
-                self._packed[key] = ops.pack_tower(self.state_dict(), self.config, self.operand_dtype(), self.device,
-                                                   select_layer)
+                self._packed[key] = self._pack(select_layer)
         return self._packed[key]
 
     @torch.no_grad()
@@ -148,7 +168,7 @@ class HipCLIPVisionModel(nn.Module):
             split = self.force_streams == 2 and n >= 2
         ks = {} if self.k_split is None else {"k_split": tuple(self.k_split)}      # None: the call of before, argument for argument
         if not split:
-            return ops.tower_forward(self.packed(select_layer), pixel_values, out_dtype, keep_cls, **ks)
+            return self._run(self.packed(select_layer), pixel_values, out_dtype, keep_cls, **ks)
         # two independent half batches on two streams: fills each kernel's last partial round.  The first half stays on the CALLER's
         # stream, only the second gets a stream of its own: ROCm maps HIP streams onto 4 hardware queues by default, and with two
         # private tower streams + the caller's + a tail stream + RCCL's, the two halves landed on ONE queue and serialised (round 4:
@@ -158,16 +178,43 @@ class HipCLIPVisionModel(nn.Module):
         cur = torch.cuda.current_stream()
         side = self._streams[0]
         half = (n + 1) // 2
-        rows = self.config.num_patches + (1 if keep_cls else 0)
+        rows = self._rows(keep_cls)
         out = torch.empty((n, rows, self.config.hidden_size), dtype=out_dtype, device=pixel_values.device)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            ops.tower_forward(self.packed(select_layer, 1), pixel_values[half:], out_dtype, keep_cls, out=out[half:], **ks)
-        ops.tower_forward(self.packed(select_layer, 0), pixel_values[:half], out_dtype, keep_cls, out=out[:half], **ks)   # both halves land in one tensor
+            self._run(self.packed(select_layer, 1), pixel_values[half:], out_dtype, keep_cls, out=out[half:], **ks)
+        self._run(self.packed(select_layer, 0), pixel_values[:half], out_dtype, keep_cls, out=out[:half], **ks)   # both halves land in one tensor
         pixel_values.record_stream(side)
         out.record_stream(side)
         cur.wait_stream(side)
         return out
+
+
+class HipCLIPVisionModel(HipVisionModelBase):
+    """Parameter container with HF ``CLIPVisionModel`` state-dict keys (transformers-4.37 names,
+    ``vision_model.`` prefix; prefix-free 5.x keys are accepted on load) whose forward is the HIP
+    tower."""
+    TOP_LEVEL = ("embeddings", "pre_layrnorm", "encoder", "post_layernorm")
+
+    def __init__(self, config: VisionConfig, compute_dtype: torch.dtype = torch.bfloat16):
+        super().__init__(config, compute_dtype)
+        self.vision_model = _VisionTransformer(config)
+        self.requires_grad_(False)
+
+    def _anchor(self) -> torch.Tensor:
+        return self.vision_model.embeddings.class_embedding
+
+    def _pack(self, select_layer: int) -> ops.PackedTower:
+        return ops.pack_tower(self.state_dict(), self.config, self.operand_dtype(), self.device, select_layer)
+
+    def _share(self, base: ops.PackedTower) -> ops.PackedTower:
+        return ops.PackedTower(base.cfg, base.dtype, base.layers_run, base.tensors, base.desc, act=base.act)
+
+    def _run(self, pt, pixel_values, out_dtype, keep_cls, **kw):
+        return ops.tower_forward(pt, pixel_values, out_dtype, keep_cls, **kw)
+
+    def _rows(self, keep_cls: bool) -> int:
+        return self.config.num_patches + (1 if keep_cls else 0)
 
     @torch.no_grad()
     def forward(self, pixel_values: torch.Tensor, output_hidden_states: bool = False, **_):

@@ -19,7 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .weights import VisionConfig, AdapterConfig, strip_tower_prefix, sub_state
+from .weights import VisionConfig, SiglipVisionConfig, AdapterConfig, strip_tower_prefix, sub_state
 
 LOG2E = 1.4426950408889634   # slime_attention takes q pre-scaled by head_dim^-0.5 * log2(e)
 
@@ -345,11 +345,19 @@ def tower_host_tensors(state_dict: Dict[str, torch.Tensor], cfg: VisionConfig, d
     if dtype not in (None, torch.bfloat16, torch.float16):
         raise ValueError("tower compute dtype must be bf16 or fp16 (MFMA operand type); fp32 I/O is supported")
     sd = strip_tower_prefix(state_dict)
-    D, L = cfg.hidden_size, layers_for_select(cfg, select_layer)
-    P2 = 3 * cfg.patch_size * cfg.patch_size
-    kpad = (P2 + 63) // 64 * 64
-    scale = cfg.head_dim ** -0.5 * LOG2E                     # logits in log2 units (slime_attention contract)
+    L = layers_for_select(cfg, select_layer)
+    f32, tt = _host_casts(dtype)
+    T: Dict[str, torch.Tensor] = {
+        "patch_w": _conv_matrix(sd, cfg, tt), "cls": f32(sd["embeddings.class_embedding"]),
+        "pos": f32(sd["embeddings.position_embedding.weight"]),
+        "pre_ln_w": f32(sd["pre_layrnorm.weight"]), "pre_ln_b": f32(sd["pre_layrnorm.bias"]),
+    }
+    _layer_host_tensors(T, sd, cfg, dtype, L)
+    return T
 
+
+def _host_casts(dtype: Optional[torch.dtype]):
+    """(fp32 cast, T cast) of the host packers; dtype = None: both float64 (nothing is rounded)."""
     def f32(t):
         t = t.detach().cpu()
         return (t.double() if dtype is None else t.float()).contiguous()
@@ -358,13 +366,23 @@ def tower_host_tensors(state_dict: Dict[str, torch.Tensor], cfg: VisionConfig, d
         t = t.detach().cpu()
         return (t.double() if dtype is None else t.float().to(dtype)).contiguous()
 
-    pw = torch.zeros((D, kpad), dtype=torch.float32)
+    return f32, tt
+
+
+def _conv_matrix(sd, cfg, tt) -> torch.Tensor:
+    """The patch-embed conv weight as a [D, kpad] matrix (column order Conv2d.weight.flatten(1), zero padded to a multiple of 64)."""
+    D, P2 = cfg.hidden_size, 3 * cfg.patch_size * cfg.patch_size
+    pw = torch.zeros((D, (P2 + 63) // 64 * 64), dtype=torch.float32)
     pw[:, :P2] = sd["embeddings.patch_embedding.weight"].detach().float().cpu().reshape(D, P2)
-    T: Dict[str, torch.Tensor] = {
-        "patch_w": tt(pw), "cls": f32(sd["embeddings.class_embedding"]),
-        "pos": f32(sd["embeddings.position_embedding.weight"]),
-        "pre_ln_w": f32(sd["pre_layrnorm.weight"]), "pre_ln_b": f32(sd["pre_layrnorm.bias"]),
-    }
+    return tt(pw)
+
+
+def _layer_host_tensors(T: Dict[str, torch.Tensor], sd, cfg, dtype: Optional[torch.dtype], L: int) -> None:
+    """The per-layer part of ``tower_host_tensors`` (the CLIP and SigLIP layouts share the layer keys): adds the stacked, folded
+    tensors of the first ``L`` layers to ``T``."""
+    D = cfg.hidden_size
+    scale = cfg.head_dim ** -0.5 * LOG2E                     # logits in log2 units (slime_attention contract)
+    f32, tt = _host_casts(dtype)
     if L > 0:
         p = "encoder.layers.{}."
 
@@ -392,7 +410,6 @@ def tower_host_tensors(state_dict: Dict[str, torch.Tensor], cfg: VisionConfig, d
         T["w_fc1"], T["b_fc1"], T["colsum_fc1"] = host_stack(w1), host_stack(b1), host_stack(c1)
         T["w_o"], T["b_o"] = stack(p + "self_attn.out_proj.weight", tt), stack(p + "self_attn.out_proj.bias", f32)
         T["w_fc2"], T["b_fc2"] = stack(p + "mlp.fc2.weight", tt), stack(p + "mlp.fc2.bias", f32)
-    return T
 
 
 def pack_tower(state_dict: Dict[str, torch.Tensor], cfg: VisionConfig, dtype: torch.dtype, device,
@@ -402,8 +419,7 @@ def pack_tower(state_dict: Dict[str, torch.Tensor], cfg: VisionConfig, dtype: to
     if dtype not in (torch.bfloat16, torch.float16):
         raise ValueError("tower compute dtype must be bf16 or fp16 (MFMA operand type); fp32 I/O is supported")
     act = tower_act(cfg)
-    D, Fi, L = cfg.hidden_size, cfg.intermediate_size, layers_for_select(cfg, select_layer)
-    kpad = (3 * cfg.patch_size * cfg.patch_size + 63) // 64 * 64
+    L = layers_for_select(cfg, select_layer)
     T: Dict[str, torch.Tensor] = {k: v.to(device).contiguous() for k, v in tower_host_tensors(state_dict, cfg, dtype, select_layer).items()}
     if L > 0:
         # fragment-order images (the direct-B kernel loads them straight into registers, the LDS-staged kernels DMA from them);
@@ -415,16 +431,23 @@ def pack_tower(state_dict: Dict[str, torch.Tensor], cfg: VisionConfig, dtype: to
             raise _lib.SlimeHipError("pack_tower: weights are packed on the GPU (slime_gemm_pack_b): slime_amd has no CPU path")
         raise ValueError("pack_tower: the patch-embed weight could not be packed (hidden size and padded patch size must be multiples of 64)")
     T["patch_w"] = None
-    d = _lib.VitDesc()
-    d.hidden, d.inter, d.heads, d.layers_run = D, Fi, cfg.num_attention_heads, L
-    d.image, d.patch, d.kpad, d.dtype, d.eps = cfg.image_size, cfg.patch_size, kpad, dtype_code(dtype), cfg.layer_norm_eps
-    for name in ("patch_w", "cls", "pos", "pre_ln_w", "pre_ln_b", "w_qkv", "b_qkv", "colsum_qkv", "w_o", "b_o",
-                 "w_fc1", "b_fc1", "colsum_fc1", "w_fc2", "b_fc2", "w_qkv_frag", "w_o_frag", "w_fc1_frag", "w_fc2_frag", "patch_w_frag"):
-        setattr(d, name, T[name].data_ptr() if name in T and T[name] is not None else None)
+    d = _vit_desc(T, cfg, dtype, L)
     # the driver's own validation, at PACK time: a geometry the fused front end cannot run (more than 24 patches per side, image
     # not a multiple of 8, ...) is refused here with the limit named, not by the first forward
     _lib.check(_lib.load().slime_vit_check(C.byref(d)), "pack_tower")
     return PackedTower(cfg, dtype, L, T, d, act=act)
+
+
+def _vit_desc(T: Dict[str, Optional[torch.Tensor]], cfg, dtype: torch.dtype, L: int) -> "_lib.VitDesc":
+    """slime_vit_desc over the packed device tensors ``T`` (a tensor that is absent or None leaves its field NULL)."""
+    d = _lib.VitDesc()
+    d.hidden, d.inter, d.heads, d.layers_run = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, L
+    d.image, d.patch, d.dtype, d.eps = cfg.image_size, cfg.patch_size, dtype_code(dtype), cfg.layer_norm_eps
+    d.kpad = (3 * cfg.patch_size * cfg.patch_size + 63) // 64 * 64
+    for name in ("patch_w", "cls", "pos", "pre_ln_w", "pre_ln_b", "w_qkv", "b_qkv", "colsum_qkv", "w_o", "b_o",
+                 "w_fc1", "b_fc1", "colsum_fc1", "w_fc2", "b_fc2", "w_qkv_frag", "w_o_frag", "w_fc1_frag", "w_fc2_frag", "patch_w_frag"):
+        setattr(d, name, T[name].data_ptr() if name in T and T[name] is not None else None)
+    return d
 
 
 def tower_forward(pt: PackedTower, pixels: torch.Tensor, out_dtype: Optional[torch.dtype] = None,
@@ -512,6 +535,133 @@ def tower_hidden_states(pt: PackedTower, pixels: torch.Tensor) -> torch.Tensor:
         return states
     _lib.check(lib.slime_vit_forward_states(C.byref(pt.desc), pixels.data_ptr(), dtype_code(pixels.dtype), n, states.data_ptr(), base,
                                             avail, _stream()), "slime_vit_forward_states")
+    return states
+
+
+# ------------------------------------------------------------------------------------------------
+# SigLIP towers (HF SiglipVisionModel, patch 16, head_dim 64): slime_siglip_forward
+# ------------------------------------------------------------------------------------------------
+SIGLIP_ACT = "gelu_pytorch_tanh"
+SIGLIP_MAX_GRID = 24
+
+
+@dataclass
+class PackedSiglipTower:
+    cfg: SiglipVisionConfig
+    dtype: torch.dtype
+    layers_run: int
+    tensors: Dict[str, torch.Tensor]
+    desc: _lib.VitDesc
+    ws: Workspace = field(default_factory=Workspace)
+
+    @property
+    def device(self):
+        return self.tensors["pos"].device
+
+
+def check_siglip_config(cfg: SiglipVisionConfig) -> None:
+    """The towers the SigLIP path runs, refused by name otherwise (no device work): the tanh-form GELU, head_dim 64, at most 24
+    patches per side, an intermediate size that is a multiple of 128.  (so400m-patch14: head_dim 72, 4304, 27 per side;
+    base-patch16-512: 32 per side.)"""
+    if cfg.hidden_act != SIGLIP_ACT:
+        raise ValueError(f"SigLIP vision tower hidden_act={cfg.hidden_act!r} is not supported: the HIP SigLIP path computes "
+                         f"{SIGLIP_ACT!r} only")
+    if cfg.num_attention_heads <= 0 or cfg.hidden_size % cfg.num_attention_heads or cfg.head_dim != 64:
+        raise ValueError(f"SigLIP vision tower head_dim={cfg.hidden_size / max(cfg.num_attention_heads, 1):g} (hidden_size {cfg.hidden_size} / "
+                         f"{cfg.num_attention_heads} heads) is not supported: head_dim must be 64")
+    if cfg.patch_size <= 0 or cfg.image_size % cfg.patch_size or cfg.grid > SIGLIP_MAX_GRID:
+        raise ValueError(f"SigLIP vision tower with {cfg.image_size / max(cfg.patch_size, 1):g} patches per side (image_size {cfg.image_size} / "
+                         f"patch_size {cfg.patch_size}) is not supported: at most {SIGLIP_MAX_GRID} whole patches per side")
+    if cfg.intermediate_size % 128:
+        raise ValueError(f"SigLIP vision tower intermediate_size={cfg.intermediate_size} is not supported: it must be a multiple of 128")
+
+
+def siglip_host_tensors(state_dict: Dict[str, torch.Tensor], cfg: SiglipVisionConfig, dtype: Optional[torch.dtype],
+                        select_layer: int = -2) -> Dict[str, torch.Tensor]:
+    """``tower_host_tensors`` for the SigLIP layout: the conv weight as a [D, kpad] matrix, ``pos`` = position_embedding +
+    patch_embedding.bias [P, D] (one fp32 addition per element at pack time; float64 with dtype = None), and the same per-layer
+    tensors.  ``post_layernorm.*`` and ``head.*`` are not read."""
+    if dtype not in (None, torch.bfloat16, torch.float16):
+        raise ValueError("tower compute dtype must be bf16 or fp16 (MFMA operand type); fp32 I/O is supported")
+    sd = strip_tower_prefix(state_dict)
+    L = layers_for_select(cfg, select_layer)
+    f32, tt = _host_casts(dtype)
+    pos = f32(sd["embeddings.position_embedding.weight"]) + f32(sd["embeddings.patch_embedding.bias"])[None, :]
+    T: Dict[str, torch.Tensor] = {"patch_w": _conv_matrix(sd, cfg, tt), "pos": pos.contiguous()}
+    _layer_host_tensors(T, sd, cfg, dtype, L)
+    return T
+
+
+def pack_siglip_tower(state_dict: Dict[str, torch.Tensor], cfg: SiglipVisionConfig, dtype: torch.dtype, device,
+                      select_layer: int = -2) -> PackedSiglipTower:
+    """HF SiglipVisionModel state dict (either key generation) -> device tensors in the kernels' layout, as ``pack_tower``: LayerNorm
+    gamma / beta folded into q/k/v and fc1, pos', the fragment-order images, the colsums; slime_siglip_check at pack time."""
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("tower compute dtype must be bf16 or fp16 (MFMA operand type); fp32 I/O is supported")
+    check_siglip_config(cfg)
+    L = layers_for_select(cfg, select_layer)
+    T: Dict[str, torch.Tensor] = {k: v.to(device).contiguous() for k, v in siglip_host_tensors(state_dict, cfg, dtype, select_layer).items()}
+    if L > 0:
+        pack_static(T, ("w_qkv", "w_o", "w_fc1", "w_fc2"))
+    T["patch_w_frag"] = pack_b_frag(T["patch_w"])          # the front end (slime_patch_embed_plain) reads this image only
+    if T["patch_w_frag"] is None:
+        if not T["patch_w"].is_cuda:
+            raise _lib.SlimeHipError("pack_siglip_tower: weights are packed on the GPU (slime_gemm_pack_b): slime_amd has no CPU path")
+        raise ValueError("pack_siglip_tower: the patch-embed weight could not be packed (hidden size must be a multiple of 64)")
+    T["patch_w"] = None
+    d = _vit_desc(T, cfg, dtype, L)
+    _lib.check(_lib.load().slime_siglip_check(C.byref(d)), "pack_siglip_tower")
+    return PackedSiglipTower(cfg, dtype, L, T, d)
+
+
+def _siglip_pixels(pt: PackedSiglipTower, pixels: torch.Tensor) -> torch.Tensor:
+    _require_cuda(pixels, "pixels")
+    cfg = pt.cfg
+    if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != cfg.image_size or pixels.shape[3] != cfg.image_size:
+        raise ValueError(f"Input image size ({tuple(pixels.shape[2:])}) doesn't match model ({cfg.image_size}*{cfg.image_size}).")
+    if pixels.dtype not in (torch.float32, pt.dtype):
+        pixels = pixels.to(pt.dtype)
+    return pixels.contiguous()
+
+
+def _siglip_call(pt: PackedSiglipTower, pixels, out, hidden, states, k_split) -> None:
+    lib = _lib.load()
+    n, ks = pixels.shape[0], None
+    if k_split is not None:
+        if len(k_split) != 4:
+            raise ValueError("siglip_tower_forward: k_split is (qkv, out_proj, fc1, fc2)")
+        ks = _lib.VitKsplit(*(int(v) for v in k_split))
+        need = lib.slime_siglip_ksplit_workspace_bytes(C.byref(pt.desc), n, C.byref(ks))
+    else:
+        need = lib.slime_siglip_workspace_bytes(C.byref(pt.desc), n)
+    base, avail = pt.ws.aligned(need, pixels.device)
+    _lib.check(lib.slime_siglip_forward(C.byref(pt.desc), pixels.data_ptr(), dtype_code(pixels.dtype), n, _ptr(out),
+                                        dtype_code(out.dtype) if out is not None else _lib.F32, _ptr(hidden), _ptr(states),
+                                        C.byref(ks) if ks is not None else None, base, avail, _stream()), "slime_siglip_forward")
+
+
+def siglip_tower_forward(pt: PackedSiglipTower, pixels: torch.Tensor, out_dtype: Optional[torch.dtype] = None,
+                         want_hidden: bool = False, out: Optional[torch.Tensor] = None, k_split: Optional[Sequence[int]] = None):
+    """pixels [N,3,S,S] (fp32 or the tower dtype) -> hidden_states[select_layer] [N, P, D] in out_dtype: all P tokens (written into
+    ``out`` if given).  k_split as in :func:`tower_forward`."""
+    pixels = _siglip_pixels(pt, pixels)
+    cfg, n = pt.cfg, pixels.shape[0]
+    out_dtype = out_dtype or pixels.dtype
+    if out is None:
+        out = torch.empty((n, cfg.num_patches, cfg.hidden_size), dtype=out_dtype, device=pixels.device)
+    elif tuple(out.shape) != (n, cfg.num_patches, cfg.hidden_size) or out.dtype != out_dtype or not out.is_contiguous():
+        raise ValueError("siglip_tower_forward: out must be a contiguous [N, P, hidden] tensor of the output dtype")
+    hidden = torch.empty((n, cfg.num_patches, cfg.hidden_size), dtype=torch.float32, device=pixels.device) if want_hidden else None
+    _siglip_call(pt, pixels, out, hidden, None, k_split)
+    return (out, hidden) if want_hidden else out
+
+
+def siglip_tower_hidden_states(pt: PackedSiglipTower, pixels: torch.Tensor, k_split: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """pixels [N,3,S,S] -> fp32 [layers_run + 1, N, P, D]: HF's hidden_states of ONE tower pass (entry 0 = the embeddings)."""
+    pixels = _siglip_pixels(pt, pixels)
+    states = torch.empty((pt.layers_run + 1, pixels.shape[0], pt.cfg.num_patches, pt.cfg.hidden_size), dtype=torch.float32,
+                         device=pixels.device)
+    _siglip_call(pt, pixels, None, None, states, k_split)
     return states
 
 

@@ -127,6 +127,88 @@ def make_tower_state_dict(cfg: VisionConfig = CLIP_L_336, seed: int = 1234) -> D
     return sd
 
 
+@dataclass(frozen=True)
+class SiglipVisionConfig:
+    """Geometry of a SigLIP vision tower (HF ``SiglipVisionConfig`` field names; defaults: siglip-large-patch16-384).  No class
+    token: ``seq_len == num_patches``."""
+    hidden_size: int = 1024
+    intermediate_size: int = 4096
+    num_hidden_layers: int = 24
+    num_attention_heads: int = 16
+    image_size: int = 384
+    patch_size: int = 16
+    layer_norm_eps: float = 1e-6
+    hidden_act: str = "gelu_pytorch_tanh"
+
+    @property
+    def grid(self) -> int:
+        return self.image_size // self.patch_size
+
+    @property
+    def num_patches(self) -> int:
+        return self.grid * self.grid
+
+    @property
+    def seq_len(self) -> int:
+        return self.num_patches
+
+    @property
+    def head_dim(self) -> int:
+        return self.hidden_size // self.num_attention_heads
+
+    def to_dict(self):
+        return asdict(self)
+
+
+SIGLIP_L_384 = SiglipVisionConfig()
+# the TINY tower's widths on a patch-16 grid of 24 x 24 (S = 576: the adapter's token grid)
+SIGLIP_TINY = SiglipVisionConfig(hidden_size=128, intermediate_size=512, num_hidden_layers=3, num_attention_heads=2)
+
+
+def make_siglip_state_dict(cfg: SiglipVisionConfig = SIGLIP_L_384, seed: int = 1234, head: bool = True) -> Dict[str, torch.Tensor]:
+    """fp32 state dict with HF ``SiglipVisionModel`` key names (``vision_model.`` prefix, as make_tower_state_dict): a conv bias, a
+    position table of P rows, no class embedding and no pre-LayerNorm; ``post_layernorm.*`` and (``head``) the pooling head
+    ``head.*`` are part of a checkpoint and are never run here.  Scales as in :func:`make_tower_state_dict`."""
+    g = _gen(seed)
+    D, F, P = cfg.hidden_size, cfg.intermediate_size, cfg.patch_size
+    sd: Dict[str, torch.Tensor] = {}
+    p = "vision_model."
+    sd[p + "embeddings.patch_embedding.weight"] = _normal(g, (D, 3, P, P), 0.02)
+    sd[p + "embeddings.patch_embedding.bias"] = _normal(g, (D,), 0.05)
+    sd[p + "embeddings.position_embedding.weight"] = _normal(g, (cfg.num_patches, D), 0.02)
+    depth_scale = (2 * cfg.num_hidden_layers) ** -0.5
+    for i in range(cfg.num_hidden_layers):
+        q = f"{p}encoder.layers.{i}."
+        sd[q + "layer_norm1.weight"] = _normal(g, (D,), 0.1, 1.0)
+        sd[q + "layer_norm1.bias"] = _normal(g, (D,), 0.05)
+        for name, std in (("q_proj", D ** -0.5), ("k_proj", D ** -0.5),
+                          ("v_proj", D ** -0.5), ("out_proj", D ** -0.5 * depth_scale * 2.0)):
+            sd[q + f"self_attn.{name}.weight"] = _normal(g, (D, D), std)
+            sd[q + f"self_attn.{name}.bias"] = _normal(g, (D,), 0.02)
+        sd[q + "layer_norm2.weight"] = _normal(g, (D,), 0.1, 1.0)
+        sd[q + "layer_norm2.bias"] = _normal(g, (D,), 0.05)
+        sd[q + "mlp.fc1.weight"] = _normal(g, (F, D), (2 * D) ** -0.5 * 2.0)
+        sd[q + "mlp.fc1.bias"] = _normal(g, (F,), 0.02)
+        sd[q + "mlp.fc2.weight"] = _normal(g, (D, F), F ** -0.5 * depth_scale * 2.0)
+        sd[q + "mlp.fc2.bias"] = _normal(g, (D,), 0.02)
+    sd[p + "post_layernorm.weight"] = _normal(g, (D,), 0.1, 1.0)
+    sd[p + "post_layernorm.bias"] = _normal(g, (D,), 0.05)
+    if head:
+        h = p + "head."
+        sd[h + "probe"] = _normal(g, (1, 1, D), 0.02)
+        sd[h + "attention.in_proj_weight"] = _normal(g, (3 * D, D), D ** -0.5)
+        sd[h + "attention.in_proj_bias"] = _normal(g, (3 * D,), 0.02)
+        sd[h + "attention.out_proj.weight"] = _normal(g, (D, D), D ** -0.5)
+        sd[h + "attention.out_proj.bias"] = _normal(g, (D,), 0.02)
+        sd[h + "layernorm.weight"] = _normal(g, (D,), 0.1, 1.0)
+        sd[h + "layernorm.bias"] = _normal(g, (D,), 0.05)
+        sd[h + "mlp.fc1.weight"] = _normal(g, (F, D), D ** -0.5)
+        sd[h + "mlp.fc1.bias"] = _normal(g, (F,), 0.02)
+        sd[h + "mlp.fc2.weight"] = _normal(g, (D, F), F ** -0.5)
+        sd[h + "mlp.fc2.bias"] = _normal(g, (D,), 0.02)
+    return sd
+
+
 def canonical_tower_key(key: str) -> str:
     """Map either HF naming generation onto the prefix-free form used internally."""
     return key[len("vision_model."):] if key.startswith("vision_model.") else key
