@@ -192,6 +192,19 @@ int slime_patch_embed_prenorm(const void* pixels, int pix_dtype, const void* pat
 int slime_patch_embed_plain(const void* pixels, int pix_dtype, const void* patch_w_frag, const float* pos, float* h, void* x16,
                             void* lo8, float* stats, int dtype, int n, int image, int patch, int kpad, int D, void* stream);
 
+/* The front end's third form, for towers with input-independent rows in front of the patches and no pre-LayerNorm (HF
+ * Dinov2Embeddings / Dinov2WithRegistersEmbeddings: class token, then R register tokens, then the patches):
+ *   h[n, n_prefix + P, D] = cat(prefix[n_prefix, D], conv_{patch x patch, stride patch}(pixels) + pos'[P, D])
+ * prefix f32 [n_prefix, D]: row 0 = cls_token + position 0, rows 1.. = the register tokens as they are (they carry no position);
+ * pos' f32 [P, D] = the patch rows of the position table (interpolated to this grid at pack time) + the conv bias.  The token of
+ * patch p is row n_prefix + p of its crop.  The prefix rows are stored with no arithmetic beyond the rounding to T (x16, lo8; h is
+ * the table's own bits), by the workgroup that owns the crop's first patch rows; their stats are the sums of the ROUNDED row, as
+ * for every other row.  1 <= n_prefix <= 17.  Same staging, re-tiling and MFMA loop, same outputs (over n * (n_prefix + P) rows)
+ * and the same geometry limits as slime_patch_embed_prenorm. */
+int slime_patch_embed_prefix(const void* pixels, int pix_dtype, const void* patch_w_frag, const float* prefix, int n_prefix,
+                             const float* pos, float* h, void* x16, void* lo8, float* stats, int dtype, int n, int image, int patch,
+                             int kpad, int D, void* stream);
+
 /* Fused multi-head attention, softmax(Q K^T) V with fp32 online softmax; Q is expected PRE-SCALED
  * by head_dim^-0.5 * log2(e) (SLIME_ATTN_Q_PRESCALE, folded into the q projection weights and bias at pack
  * time): the logits then arrive in log2 units and the kernels evaluate 2^x with v_exp_f32 directly.
@@ -555,6 +568,30 @@ size_t slime_siglip_workspace_bytes(const slime_vit_desc* d, int n_crops);
 size_t slime_siglip_ksplit_workspace_bytes(const slime_vit_desc* d, int n_crops, const slime_vit_ksplit* ks);
 int slime_siglip_forward(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n_crops, void* out, int out_dtype,
                          float* hidden_f32, float* states_f32, const slime_vit_ksplit* ks, void* ws, size_t ws_bytes, void* stream);
+
+/* DINOv2 vision towers (HF Dinov2Model / Dinov2WithRegistersModel, ViT-B/14 and ViT-L/14: head_dim 64, MLP 4 x width, exact GELU):
+ * the layer loop of slime_vit_forward* over a sequence of S = n_prefix + P rows per crop
+ *   [cls + pos[0]] [R register tokens, no position] [P patches: conv + conv bias + pos],   n_prefix = 1 + R,  1 <= n_prefix <= 17,
+ * no pre-LayerNorm, behind slime_patch_embed_prefix, with fc1's epilogue SLIME_EPI_BIAS_GELU_T.  They take slime_vit_desc with
+ * these conventions: cls is REQUIRED and carries the prefix table f32 [n_prefix, D] (row 0 = cls_token + position 0, then the
+ * register tokens); pre_ln_w and pre_ln_b MUST be NULL (refused otherwise, the field named); pos is pos' f32 [P, D] = the patch rows
+ * of the position table, interpolated to the run grid at pack time (bicubic, HF's arguments; antialias only in the registers model),
+ * + patch_embeddings.projection.bias; every other field as for the CLIP entries.  LayerScale is linear and folded at pack time:
+ *   h += lambda1 * (ctx Wo^T + b)   ->  w_o  = T(diag(lambda1) Wo),  b_o  = lambda1 * b,
+ *   h += lambda2 * (ff W2^T + b)    ->  w_fc2 = T(diag(lambda2) W2), b_fc2 = lambda2 * b,
+ * so the residual epilogue is the one every tower uses.  The final layernorm is never run.
+ *   out        [n, keep_prefix ? S : P, D] of out_dtype: keep_prefix = 0 returns the P patch rows (slime_gather_rows_split from row
+ *              n_prefix of every crop), keep_prefix = 1 all S rows, of the last state run;
+ *   hidden_f32 [n, S, D]: the same state in fp32, all rows;
+ *   states_f32 [layers_run + 1, n, S, D]: HF's hidden_states (entry 0 = the embeddings, entry i = after layer i).
+ * Any of the three may be NULL, one is required.  ks as in slime_siglip_forward.  ws: slime_dinov2_workspace_bytes, or
+ * slime_dinov2_ksplit_workspace_bytes with ks.  slime_dinov2_check: the host-only validation every forward starts with. */
+int slime_dinov2_check(const slime_vit_desc* d, int n_prefix);
+size_t slime_dinov2_workspace_bytes(const slime_vit_desc* d, int n_prefix, int n_crops);
+size_t slime_dinov2_ksplit_workspace_bytes(const slime_vit_desc* d, int n_prefix, int n_crops, const slime_vit_ksplit* ks);
+int slime_dinov2_forward(const slime_vit_desc* d, int n_prefix, const void* pixels, int pix_dtype, int n_crops, void* out, int out_dtype,
+                         int keep_prefix, float* hidden_f32, float* states_f32, const slime_vit_ksplit* ks, void* ws, size_t ws_bytes,
+                         void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Resampler (sampler.py:91-173) with kv_proj = proj = Identity, as post_qformer / GatedBlock.attn

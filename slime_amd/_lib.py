@@ -140,6 +140,8 @@ _SIGNATURES = {
                                           c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "slime_patch_embed_plain": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                         c_int, c_int, c_int, c_void_p]),
+    "slime_patch_embed_prefix": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                         c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "slime_gemm_ex": (c_int, [_P(GemmArgs), c_void_p]),
     "slime_gemm_ksplit_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "slime_gemm_ksplit": (c_int, [_P(GemmArgs), c_int, c_void_p, c_size_t, c_void_p]),
@@ -204,6 +206,11 @@ _SIGNATURES = {
     "slime_siglip_ksplit_workspace_bytes": (c_size_t, [_P(VitDesc), c_int, _P(VitKsplit)]),
     "slime_siglip_forward": (c_int, [_P(VitDesc), c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, _P(VitKsplit), c_void_p,
                                      c_size_t, c_void_p]),
+    "slime_dinov2_check": (c_int, [_P(VitDesc), c_int]),
+    "slime_dinov2_workspace_bytes": (c_size_t, [_P(VitDesc), c_int, c_int]),
+    "slime_dinov2_ksplit_workspace_bytes": (c_size_t, [_P(VitDesc), c_int, c_int, _P(VitKsplit)]),
+    "slime_dinov2_forward": (c_int, [_P(VitDesc), c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, _P(VitKsplit),
+                                     c_void_p, c_size_t, c_void_p]),
     "slime_resampler_workspace_bytes": (c_size_t, [_P(ResamplerDesc), c_int]),
     "slime_resampler_forward": (c_int, [_P(ResamplerDesc), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                         c_size_t, c_void_p]),

@@ -67,13 +67,17 @@ struct VitPlan {
     size_t xn, qkv, ctx, ff, lo, stats, total;  // offsets (lo: the lower part of the split stream, one byte per element)
 };
 
-// The two tower forms the layer loop serves (vit_run): the CLIP layout (class token + pre-LayerNorm, S = P + 1 rows per crop) and the
-// plain one of the SigLIP towers (S = P rows behind slime_patch_embed_plain, fc1 with the tanh-form GELU).
-struct VitForm { bool plain; int fc1_epilogue; };
-static int vit_seq(const slime_vit_desc* d, bool plain) { const int g = d->image / d->patch; return g * g + (plain ? 0 : 1); }
+// The three tower forms the layer loop serves (vit_run): the CLIP layout (class token + pre-LayerNorm, S = P + 1 rows per crop), the
+// plain one of the SigLIP towers (S = P rows behind slime_patch_embed_plain, fc1 with the tanh-form GELU) and the prefix one of the
+// DINOv2 towers (n_prefix > 0: S = n_prefix + P rows behind slime_patch_embed_prefix, no pre-LayerNorm, fc1 with the exact GELU).
+struct VitForm { bool plain; int fc1_epilogue; int n_prefix = 0; };
+static int vit_seq(const slime_vit_desc* d, bool plain, int n_prefix = 0) {
+    const int g = d->image / d->patch;
+    return g * g + (n_prefix > 0 ? n_prefix : plain ? 0 : 1);
+}
 
-static VitPlan vit_plan(const slime_vit_desc* d, int n, bool plain = false) {
-    const int S = vit_seq(d, plain);
+static VitPlan vit_plan(const slime_vit_desc* d, int n, bool plain = false, int n_prefix = 0) {
+    const int S = vit_seq(d, plain, n_prefix);
     const size_t M = (size_t)n * S, D = d->hidden;
     VitPlan p{};
     size_t off = 0;
@@ -97,9 +101,13 @@ static VitPlan vit_plan(const slime_vit_desc* d, int n, bool plain = false) {
 
 int slime_patch_embed_geometry(int image, int patch, int kpad, int D, size_t* lds_out);   // patch_embed.hip: the fused front end's limits
 
-static int vit_validate(const slime_vit_desc* d, bool plain = false) {
+static int vit_validate(const slime_vit_desc* d, bool plain = false, int n_prefix = 0) {
     SLIME_REQUIRE(d, "vit: null descriptor");
-    if (plain) {                                    // the SigLIP entries: the descriptor's class-token / pre-LayerNorm fields stay empty
+    if (n_prefix > 0) {                             // the DINOv2 entries: cls carries the prefix table, the pre-LayerNorm fields stay empty
+        SLIME_REQUIRE(d->cls, "dinov2: cls is required (the prefix table [n_prefix, hidden]: class token + position 0, then the register tokens)");
+        SLIME_REQUIRE(!d->pre_ln_w, "dinov2: pre_ln_w must be NULL (a DINOv2 tower has no pre-LayerNorm)");
+        SLIME_REQUIRE(!d->pre_ln_b, "dinov2: pre_ln_b must be NULL (a DINOv2 tower has no pre-LayerNorm)");
+    } else if (plain) {                                    // the SigLIP entries: the descriptor's class-token / pre-LayerNorm fields stay empty
         SLIME_REQUIRE(!d->cls, "siglip: cls must be NULL (a SigLIP tower has no class token; slime_vit_forward* run the CLIP layout)");
         SLIME_REQUIRE(!d->pre_ln_w, "siglip: pre_ln_w must be NULL (a SigLIP tower has no pre-LayerNorm)");
         SLIME_REQUIRE(!d->pre_ln_b, "siglip: pre_ln_b must be NULL (a SigLIP tower has no pre-LayerNorm)");
@@ -112,7 +120,7 @@ static int vit_validate(const slime_vit_desc* d, bool plain = false) {
     SLIME_REQUIRE(d->patch > 0 && d->image % d->patch == 0, "vit: image %d not a multiple of patch %d", d->image, d->patch);
     TRY(slime_patch_embed_geometry(d->image, d->patch, d->kpad, d->hidden, nullptr));      // the one-launch front end's geometry limits
     SLIME_REQUIRE(d->layers_run >= 0, "vit: layers_run < 0");
-    SLIME_REQUIRE(d->patch_w_frag && d->pos && (plain || (d->cls && d->pre_ln_w && d->pre_ln_b)),
+    SLIME_REQUIRE(d->patch_w_frag && d->pos && (plain || n_prefix > 0 || (d->cls && d->pre_ln_w && d->pre_ln_b)),
                   "vit: missing embedding weights (patch_w_frag = slime_gemm_pack_b of the conv weight is required since ABI 5)");
     // a per-layer weight is given as its fragment-order image, its row-major image, or both (slime_gemm_b_frag_usable)
     SLIME_REQUIRE(d->layers_run == 0 || ((d->w_qkv || d->w_qkv_frag) && d->b_qkv && d->colsum_qkv && (d->w_o || d->w_o_frag) && d->b_o &&
@@ -174,8 +182,8 @@ static int vit_ksplit_validate(const slime_vit_desc* d, const slime_vit_ksplit* 
     return SLIME_OK;
 }
 
-static size_t vit_ksplit_partial_bytes(const slime_vit_desc* d, int n, const slime_vit_ksplit* ks, bool plain = false) {
-    const int M = n * vit_seq(d, plain);
+static size_t vit_ksplit_partial_bytes(const slime_vit_desc* d, int n, const slime_vit_ksplit* ks, bool plain = false, int n_prefix = 0) {
+    const int M = n * vit_seq(d, plain, n_prefix);
     size_t b = slime_gemm_ksplit_workspace_bytes(M, 3 * d->hidden, ks->qkv);
     auto grow = [&](size_t x) { if (x > b) b = x; };
     grow(slime_gemm_ksplit_workspace_bytes(M, d->hidden, ks->out_proj));
@@ -232,16 +240,45 @@ extern "C" int slime_siglip_forward(const slime_vit_desc* d, const void* pixels,
                    VitForm{true, SLIME_EPI_BIAS_GELU_TANH_T});
 }
 
+// DINOv2 towers: vit_run's layer loop in its prefix form (include/slime_hip.h)
+static int dinov2_prefix_ok(int n_prefix) {
+    SLIME_REQUIRE(n_prefix >= 1 && n_prefix <= 17, "dinov2: n_prefix=%d outside 1..17 (the class token and at most 16 register tokens)", n_prefix);
+    return SLIME_OK;
+}
+
+extern "C" int slime_dinov2_check(const slime_vit_desc* d, int n_prefix) {
+    TRY(dinov2_prefix_ok(n_prefix));
+    return vit_validate(d, false, n_prefix);
+}
+
+extern "C" size_t slime_dinov2_workspace_bytes(const slime_vit_desc* d, int n_prefix, int n_crops) {
+    if (!d || n_crops <= 0 || d->patch <= 0 || n_prefix < 1 || n_prefix > 17) return 0;
+    return vit_plan(d, n_crops, false, n_prefix).total;
+}
+
+extern "C" size_t slime_dinov2_ksplit_workspace_bytes(const slime_vit_desc* d, int n_prefix, int n_crops, const slime_vit_ksplit* ks) {
+    if (!d || !ks || n_crops <= 0 || d->patch <= 0 || n_prefix < 1 || n_prefix > 17) return 0;
+    return vit_plan(d, n_crops, false, n_prefix).total + vit_ksplit_partial_bytes(d, n_crops, ks, false, n_prefix);
+}
+
+extern "C" int slime_dinov2_forward(const slime_vit_desc* d, int n_prefix, const void* pixels, int pix_dtype, int n, void* out, int out_dtype,
+                                    int keep_prefix, float* hidden_f32, float* states_f32, const slime_vit_ksplit* ks, void* ws,
+                                    size_t ws_bytes, void* stream) {
+    TRY(dinov2_prefix_ok(n_prefix));
+    return vit_run(d, pixels, pix_dtype, n, out, out_dtype, keep_prefix, hidden_f32, ws, ws_bytes, stream, nullptr, states_f32, ks,
+                   VitForm{false, SLIME_EPI_BIAS_GELU_T, n_prefix});
+}
+
 static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out, int out_dtype, int keep_cls,
                    float* hidden_f32, void* ws, size_t ws_bytes, void* stream, const slime_probe* probe, float* states,
                    const slime_vit_ksplit* ks, VitForm form) {
-    TRY(vit_validate(d, form.plain));
+    TRY(vit_validate(d, form.plain, form.n_prefix));
     SLIME_REQUIRE(pixels && n > 0, "vit: bad input");
     SLIME_REQUIRE(out || hidden_f32 || states, "vit: no output requested");
     SLIME_REQUIRE(!out || out_dtype == SLIME_F32 || is16(out_dtype), "vit: bad out dtype");
     if (ks) TRY(vit_ksplit_validate(d, ks));
-    const VitPlan p = vit_plan(d, n, form.plain);
-    const size_t part_bytes = ks ? vit_ksplit_partial_bytes(d, n, ks, form.plain) : 0;      // one region of partial products behind the plan
+    const VitPlan p = vit_plan(d, n, form.plain, form.n_prefix);
+    const size_t part_bytes = ks ? vit_ksplit_partial_bytes(d, n, ks, form.plain, form.n_prefix) : 0;      // one region of partial products behind the plan
     TRY(ws_check("vit", ws, ws_bytes, p.total + part_bytes));
     // a layer GEMM: slime_gemm_ex, or the split pair where the caller asked for one (the probe brackets the GEMM as a whole)
     auto layer_gemm = [&](const slime_gemm_args& a, int splits) {
@@ -249,7 +286,8 @@ static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, i
     };
     const slime_vit_ksplit k1{1, 1, 1, 1};
     const slime_vit_ksplit& sp = ks ? *ks : k1;
-    const int S = vit_seq(d, form.plain), P = form.plain ? S : S - 1, D = d->hidden, F = d->inter;
+    const int S = vit_seq(d, form.plain, form.n_prefix), lead = form.n_prefix > 0 ? form.n_prefix : form.plain ? 0 : 1;   // rows before the patches
+    const int P = S - lead, D = d->hidden, F = d->inter;
     const int M = n * S;
     char* w = (char*)ws;
     void* xn = w + p.xn;
@@ -265,7 +303,11 @@ static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, i
     // patch embed (MFMA conv), class token, position table, pre-LayerNorm and the first folded LN1's operand + partial sums: ONE launch
     // (no fp32 rows: h = NULL)
     // -- or, in the plain form, patch embed + position table alone (slime_patch_embed_plain: S = P rows per crop)
-    if (form.plain)
+    // -- or, in the prefix form, the same behind n_prefix table rows (slime_patch_embed_prefix: S = n_prefix + P rows per crop)
+    if (form.n_prefix > 0)
+        TRY(slime_patch_embed_prefix(pixels, pix_dtype, d->patch_w_frag, d->cls, form.n_prefix, d->pos, nullptr, xn, lo, stats, dt, n, d->image,
+                                     d->patch, d->kpad, D, stream));
+    else if (form.plain)
         TRY(slime_patch_embed_plain(pixels, pix_dtype, d->patch_w_frag, d->pos, nullptr, xn, lo, stats, dt, n, d->image, d->patch, d->kpad, D,
                                     stream));
     else
@@ -326,9 +368,9 @@ static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, i
     if (hidden_f32) TRY(slime_gather_rows_split(xn, lo, dt, S, 0, hidden_f32, SLIME_F32, n, S, D, stream));
     if (out) {
         // feature_select: 'patch' drops the class token (clip_encoder.py:38-39), cast to out dtype (:52,56); the plain form has none:
-        // all S = P rows
+        // all S = P rows; the prefix form drops its n_prefix rows (keep_prefix = 0) or none
         const bool all_rows = keep_cls || form.plain;
-        TRY(slime_gather_rows_split(xn, lo, dt, S, all_rows ? 0 : 1, out, out_dtype, n, all_rows ? S : P, D, stream));
+        TRY(slime_gather_rows_split(xn, lo, dt, S, all_rows ? 0 : lead, out, out_dtype, n, all_rows ? S : P, D, stream));
     }
     return SLIME_OK;
 }

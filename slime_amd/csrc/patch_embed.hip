@@ -25,6 +25,11 @@
 // The SigLIP towers (no class token, no pre-LayerNorm, a conv bias) run the second compile-time form of the same body, steps 1-3
 // shared:  h[n, P, D] = conv16x16/16(pixels) + pos'[P, D]  (HF SiglipVisionEmbeddings.forward; pos' = position_embedding +
 // patch_embedding.bias, added at pack time), slime_patch_embed_plain.
+//
+// The DINOv2 towers (class token and R register tokens, no pre-LayerNorm, a conv bias) run the third form:
+//   h[n, n_prefix + P, D] = cat(prefix[n_prefix, D], conv14x14/14(pixels) + pos'[P, D])  (HF Dinov2Embeddings.forward; prefix row 0 =
+//   cls_token + position 0, then the register tokens as they are; pos' = interpolated patch positions + conv bias, both made at pack
+//   time), slime_patch_embed_prefix.
 #include "gemm_shared.h"
 
 namespace {
@@ -42,6 +47,7 @@ struct PEArgs {
     const void* px; const char* wf; const float* cls; const float* pos; const float* ln_w; const float* ln_b; float eps;
     float* h; char* x16; char* lo; float* stats;
     int n, image, patch, kpad, g;
+    int npre;                            // the prefix form's row count (in the struct's tail padding: the other forms' arguments keep their layout)
 };
 
 __host__ __device__ constexpr size_t pe_align16(size_t x) { return (x + 15) & ~(size_t)15; }
@@ -94,12 +100,48 @@ __device__ __forceinline__ void pe_cls_row(const PEArgs& a, const long grow, con
     }
 }
 
-// The front end's two compile-time forms share staging, re-tiling and the MFMA loop:
-//   PLAIN = false  the CLIP form above (class row, + position row, pre-LayerNorm);
-//   PLAIN = true   h[n, P, D] = conv(pixels) + pos'[P, D], pos' = position_embedding + conv bias (added at pack time): no class row
-//                  (output row = patch index, nothing writes a row 0), no LayerNorm (no mean / rstd, no affine) -- the SigLIP towers.
-template <typename T, typename PixT, int D, int NW, bool PLAIN>
+// Prefix row `row` of a crop, from the fp32 table a.cls[npre, D] (the prefix form): the no-LayerNorm sibling of pe_cls_row.  The row is
+// stored with no arithmetic beyond the rounding to T; stats = (sum, sum of squares) of the ROUNDED row per 64-column group.
+template <typename T, int D>
+__device__ __forceinline__ void pe_prefix_row(const PEArgs& a, const long grow, const int row, const int lane) {
+    constexpr int VPL = D / 64, VEC = (VPL >= 4) ? 4 : 2, NV = VPL / VEC, LPG = 64 / VEC;
+    const float* src = a.cls + (size_t)row * D;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = (i * 64 + lane) * VEC;
+        float sx = 0.f, sq = 0.f;
+#pragma unroll
+        for (int j = 0; j < VEC; j += 2) {
+            const float y0 = src[c + j], y1 = src[c + j + 1];
+            if (a.h) { a.h[grow * D + c + j] = y0; a.h[grow * D + c + j + 1] = y1; }
+            const unsigned pk = T::pack2(y0, y1);
+            const float r0 = T::lo(pk), r1 = T::hi(pk);
+            if (a.x16) *reinterpret_cast<unsigned*>(a.x16 + ((size_t)grow * D + c + j) * 2) = pk;
+            if (a.lo) {
+                a.lo[(size_t)grow * D + c + j] = (char)resid_delta<T>(y0, r0);
+                a.lo[(size_t)grow * D + c + j + 1] = (char)resid_delta<T>(y1, r1);
+            }
+            sx += r0; sx += r1; sq = fmaf(r0, r0, sq); sq = fmaf(r1, r1, sq);
+        }
+        if (a.stats) {
+#pragma unroll
+            for (int off = LPG / 2; off > 0; off >>= 1) { sx += __shfl_xor(sx, off); sq += __shfl_xor(sq, off); }
+            if ((lane & (LPG - 1)) == 0)
+                *reinterpret_cast<float2*>(a.stats + ((size_t)grow * (D / 64) + (c >> 6)) * 2) = make_float2(sx, sq);
+        }
+    }
+}
+
+// The front end's three compile-time forms share staging, re-tiling and the MFMA loop:
+//   PE_CLIP    the CLIP form above (class row, + position row, pre-LayerNorm);
+//   PE_PLAIN   h[n, P, D] = conv(pixels) + pos'[P, D], pos' = position_embedding + conv bias (added at pack time): no class row
+//              (output row = patch index, nothing writes a row 0), no LayerNorm (no mean / rstd, no affine) -- the SigLIP towers;
+//   PE_PREFIX  the plain epilogue behind a.npre input-independent rows per crop: output row = npre + patch index (pos' stays [P, D]),
+//              rows 0 .. npre - 1 copied from the table a.cls[npre, D] -- the DINOv2 towers.
+enum { PE_CLIP = 0, PE_PLAIN = 1, PE_PREFIX = 2 };
+template <typename T, typename PixT, int D, int NW, int FORM>
 __device__ __forceinline__ void pe_body(const PEArgs& a) {
+    constexpr bool PLAIN = FORM != PE_CLIP;                            // no LayerNorm
     constexpr int CW = D / NW, NT = CW / 64, NF = CW / 16, NP = NF / 2, NTHR = NW * 64;
     static_assert(CW % 64 == 0, "a wave owns whole 64-column groups (LayerNorm partial sums are wave local)");
     extern __shared__ __attribute__((aligned(16))) char smem_pe[];
@@ -234,9 +276,10 @@ __device__ __forceinline__ void pe_body(const PEArgs& a) {
     for (int mi = 0; mi < PE_MT; ++mi) {
         const int r = 16 * mi + li;
         ok[mi] = r < rows_valid;
-        const int t = (PLAIN ? 0 : 1) + prow0 * g + min(r, rows_valid - 1);   // token index (clamped: masked rows compute on a valid row's table)
-        grow[mi] = (long)crop * (P + (PLAIN ? 0 : 1)) + t;
-        const float* pr = a.pos + (size_t)t * D + cw0 + 8 * lg;
+        const int lead = FORM == PE_CLIP ? 1 : FORM == PE_PREFIX ? a.npre : 0;   // rows of a crop before its patches
+        const int t = lead + prow0 * g + min(r, rows_valid - 1);     // token index (clamped: masked rows compute on a valid row's table)
+        grow[mi] = (long)crop * (P + lead) + t;
+        const float* pr = a.pos + (size_t)(FORM == PE_PREFIX ? t - lead : t) * D + cw0 + 8 * lg;   // prefix form: pos' has the P patch rows only
         float s = 0.f;
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
@@ -332,19 +375,31 @@ __device__ __forceinline__ void pe_body(const PEArgs& a) {
         }
     }
     // the crop's class-token row (token 0): input independent, written by the workgroup that owns the first patch rows
-    if constexpr (!PLAIN) { if (pair == 0 && wave == 0) pe_cls_row<T, D>(a, (long)crop * (P + 1), lane); }
+    if constexpr (FORM == PE_CLIP) { if (pair == 0 && wave == 0) pe_cls_row<T, D>(a, (long)crop * (P + 1), lane); }
+    // the crop's prefix rows, one wave per row
+    if constexpr (FORM == PE_PREFIX) {
+        if (pair == 0)
+            for (int r = wave; r < a.npre; r += NW) pe_prefix_row<T, D>(a, (long)crop * (P + a.npre) + r, r, lane);
+    }
 }
 
 template <typename T, typename PixT, int D, int NW>
-__global__ void __launch_bounds__(NW * 64) patch_embed_kernel(PEArgs a) { pe_body<T, PixT, D, NW, false>(a); }
+__global__ void __launch_bounds__(NW * 64) patch_embed_kernel(PEArgs a) { pe_body<T, PixT, D, NW, PE_CLIP>(a); }
 
 template <typename T, typename PixT, int D, int NW>
-__global__ void __launch_bounds__(NW * 64) patch_embed_plain_kernel(PEArgs a) { pe_body<T, PixT, D, NW, true>(a); }
+__global__ void __launch_bounds__(NW * 64) patch_embed_plain_kernel(PEArgs a) { pe_body<T, PixT, D, NW, PE_PLAIN>(a); }
 
-template <typename T, typename PixT, int D, int NW, bool PLAIN>
+template <typename T, typename PixT, int D, int NW>
+__global__ void __launch_bounds__(NW * 64) patch_embed_prefix_kernel(PEArgs a) { pe_body<T, PixT, D, NW, PE_PREFIX>(a); }
+
+template <typename T, typename PixT, int D, int NW, int FORM>
 int launch_pe(const PEArgs& a, size_t lds, hipStream_t s) {
     const dim3 grid((unsigned)(a.n * ((a.g + 1) / 2))), block(NW * 64);
-    if constexpr (PLAIN) {
+    if constexpr (FORM == PE_PREFIX) {
+        auto kern = patch_embed_prefix_kernel<T, PixT, D, NW>;
+        SLIME_SET_LDS_ONCE(kern, 160 * 1024, "patch_embed_prefix");
+        hipLaunchKernelGGL(kern, grid, block, lds, s, a);
+    } else if constexpr (FORM == PE_PLAIN) {
         auto kern = patch_embed_plain_kernel<T, PixT, D, NW>;
         SLIME_SET_LDS_ONCE(kern, 160 * 1024, "patch_embed_plain");
         hipLaunchKernelGGL(kern, grid, block, lds, s, a);
@@ -357,13 +412,13 @@ int launch_pe(const PEArgs& a, size_t lds, hipStream_t s) {
     return SLIME_OK;
 }
 
-template <typename T, typename PixT, bool PLAIN>
+template <typename T, typename PixT, int FORM>
 int launch_pe_d(const PEArgs& a, int D, size_t lds, hipStream_t s) {
     switch (D) {
-        case 128: return launch_pe<T, PixT, 128, 2, PLAIN>(a, lds, s);
-        case 256: return launch_pe<T, PixT, 256, 4, PLAIN>(a, lds, s);
-        case 768: return launch_pe<T, PixT, 768, 6, PLAIN>(a, lds, s);        // six waves of 128 columns, as at 1024 (ViT-B widths)
-        case 1024: return launch_pe<T, PixT, 1024, 8, PLAIN>(a, lds, s);
+        case 128: return launch_pe<T, PixT, 128, 2, FORM>(a, lds, s);
+        case 256: return launch_pe<T, PixT, 256, 4, FORM>(a, lds, s);
+        case 768: return launch_pe<T, PixT, 768, 6, FORM>(a, lds, s);        // six waves of 128 columns, as at 1024 (ViT-B widths)
+        case 1024: return launch_pe<T, PixT, 1024, 8, FORM>(a, lds, s);
     }
     slime_set_error("patch_embed: D=%d unsupported (128, 256, 768, 1024)", D);
     return SLIME_EINVAL;
@@ -392,11 +447,24 @@ int slime_patch_embed_geometry(int image, int patch, int kpad, int D, size_t* ld
     return SLIME_OK;
 }
 
-// The one host body behind both entries: argument checks, geometry, launch.  plain: no class token, no pre-LayerNorm (cls / ln_w / ln_b unused).
-static int pe_run(bool plain, const void* pixels, int pix_dtype, const void* patch_w_frag, const float* cls, const float* pos,
+// The one host body behind the three entries: argument checks, geometry, launch.  PE_PLAIN: no class token, no pre-LayerNorm (cls /
+// ln_w / ln_b unused).  PE_PREFIX: cls is the prefix table [n_prefix, D], no pre-LayerNorm (ln_w / ln_b unused).
+template <typename T, typename PixT>
+static int launch_pe_form(int form, const PEArgs& a, int D, size_t lds, hipStream_t s) {
+    if (form == PE_PREFIX) return launch_pe_d<T, PixT, PE_PREFIX>(a, D, lds, s);
+    if (form == PE_PLAIN) return launch_pe_d<T, PixT, PE_PLAIN>(a, D, lds, s);
+    return launch_pe_d<T, PixT, PE_CLIP>(a, D, lds, s);
+}
+
+static int pe_run(int form, int n_prefix, const void* pixels, int pix_dtype, const void* patch_w_frag, const float* cls, const float* pos,
                   const float* ln_w, const float* ln_b, float eps, float* h, void* x16, void* lo8, float* stats,
                   int dtype, int n, int image, int patch, int kpad, int D, void* stream) {
-    SLIME_REQUIRE(pixels && patch_w_frag && pos && (plain || (cls && ln_w && ln_b)) && n > 0, "patch_embed: bad input");
+    SLIME_REQUIRE(pixels && patch_w_frag && pos && (form != PE_CLIP || (cls && ln_w && ln_b)) && n > 0, "patch_embed: bad input");
+    if (form == PE_PREFIX) {
+        SLIME_REQUIRE(cls, "patch_embed_prefix: the prefix table is required");
+        SLIME_REQUIRE(n_prefix >= 1 && n_prefix <= 17, "patch_embed_prefix: n_prefix=%d outside 1..17 (the class token and at most 16 register tokens)",
+                      n_prefix);
+    }
     SLIME_REQUIRE(h || x16, "patch_embed: no output requested (h and / or x16)");
     SLIME_REQUIRE(!lo8 || x16, "patch_embed: the split residual's lower part (lo8) comes with its upper part x16");
     SLIME_REQUIRE(!stats || x16, "patch_embed: stats are the partial sums of x16");
@@ -409,26 +477,28 @@ static int pe_run(bool plain, const void* pixels, int pix_dtype, const void* pat
                   ((uintptr_t)ln_w % 16) == 0 && ((uintptr_t)ln_b % 16) == 0 && (!h || (uintptr_t)h % 16 == 0) &&
                   (!x16 || (uintptr_t)x16 % 16 == 0) && (!lo8 || (uintptr_t)lo8 % 8 == 0) && (!stats || (uintptr_t)stats % 8 == 0),
                   "patch_embed: pointers must be 16-byte aligned");
-    PEArgs a{pixels, (const char*)patch_w_frag, cls, pos, ln_w, ln_b, eps, h, (char*)x16, (char*)lo8, stats, n, image, patch, kpad, g};
+    PEArgs a{pixels, (const char*)patch_w_frag, cls, pos, ln_w, ln_b, eps, h, (char*)x16, (char*)lo8, stats, n, image, patch, kpad, g, n_prefix};
     hipStream_t s = (hipStream_t)stream;
-    if (plain) {
-        if (dtype == SLIME_F16)
-            return pix_dtype == SLIME_F32 ? launch_pe_d<F16, float, true>(a, D, lds, s) : launch_pe_d<F16, unsigned short, true>(a, D, lds, s);
-        return pix_dtype == SLIME_F32 ? launch_pe_d<BF16, float, true>(a, D, lds, s) : launch_pe_d<BF16, unsigned short, true>(a, D, lds, s);
-    }
     if (dtype == SLIME_F16)
-        return pix_dtype == SLIME_F32 ? launch_pe_d<F16, float, false>(a, D, lds, s) : launch_pe_d<F16, unsigned short, false>(a, D, lds, s);
-    return pix_dtype == SLIME_F32 ? launch_pe_d<BF16, float, false>(a, D, lds, s) : launch_pe_d<BF16, unsigned short, false>(a, D, lds, s);
+        return pix_dtype == SLIME_F32 ? launch_pe_form<F16, float>(form, a, D, lds, s) : launch_pe_form<F16, unsigned short>(form, a, D, lds, s);
+    return pix_dtype == SLIME_F32 ? launch_pe_form<BF16, float>(form, a, D, lds, s) : launch_pe_form<BF16, unsigned short>(form, a, D, lds, s);
 }
 
 extern "C" int slime_patch_embed_prenorm(const void* pixels, int pix_dtype, const void* patch_w_frag, const float* cls, const float* pos,
                                          const float* ln_w, const float* ln_b, float eps, float* h, void* x16, void* lo8, float* stats,
                                          int dtype, int n, int image, int patch, int kpad, int D, void* stream) {
-    return pe_run(false, pixels, pix_dtype, patch_w_frag, cls, pos, ln_w, ln_b, eps, h, x16, lo8, stats, dtype, n, image, patch, kpad, D, stream);
+    return pe_run(PE_CLIP, 0, pixels, pix_dtype, patch_w_frag, cls, pos, ln_w, ln_b, eps, h, x16, lo8, stats, dtype, n, image, patch, kpad, D, stream);
 }
 
 extern "C" int slime_patch_embed_plain(const void* pixels, int pix_dtype, const void* patch_w_frag, const float* pos, float* h, void* x16,
                                        void* lo8, float* stats, int dtype, int n, int image, int patch, int kpad, int D, void* stream) {
-    return pe_run(true, pixels, pix_dtype, patch_w_frag, nullptr, pos, nullptr, nullptr, 0.f, h, x16, lo8, stats, dtype, n, image, patch, kpad,
+    return pe_run(PE_PLAIN, 0, pixels, pix_dtype, patch_w_frag, nullptr, pos, nullptr, nullptr, 0.f, h, x16, lo8, stats, dtype, n, image, patch, kpad,
                   D, stream);
+}
+
+extern "C" int slime_patch_embed_prefix(const void* pixels, int pix_dtype, const void* patch_w_frag, const float* prefix, int n_prefix,
+                                        const float* pos, float* h, void* x16, void* lo8, float* stats, int dtype, int n, int image, int patch,
+                                        int kpad, int D, void* stream) {
+    return pe_run(PE_PREFIX, n_prefix, pixels, pix_dtype, patch_w_frag, prefix, pos, nullptr, nullptr, 0.f, h, x16, lo8, stats, dtype, n, image,
+                  patch, kpad, D, stream);
 }

@@ -83,6 +83,39 @@ class ClipImageProcessor:
     __call__ = preprocess
 
 
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+
+
+class Dinov2ImageProcessor(ClipImageProcessor):
+    """The role of HF ``BitImageProcessor``, which the DINOv2 checkpoints name in ``preprocessor_config.json``: resize the shortest
+    edge to 256 (bicubic), centre crop 224, rescale, ImageNet mean / std -- the pipeline of the class above with other constants
+    (bit-identical to transformers' PIL backend).  ``crop_size`` is the size the tower runs at."""
+
+    def __init__(self, size: int = 256, crop_size: int = 224, image_mean: Sequence[float] = IMAGENET_MEAN,
+                 image_std: Sequence[float] = IMAGENET_STD, rescale_factor: float = 1 / 255, resample: int = Image.BICUBIC):
+        super().__init__(size, crop_size, image_mean, image_std, rescale_factor)
+        self.resample = Image.Resampling(int(resample))
+
+    @classmethod
+    def from_pretrained(cls, path: str, default_crop: int = 224) -> "Dinov2ImageProcessor":
+        """Read ``preprocessor_config.json`` from a local directory; without one: a centre crop of ``default_crop`` out of a
+        shortest edge of 256 / 224 times that (the released checkpoints' ratio)."""
+        f = os.path.join(path, "preprocessor_config.json")
+        if not os.path.isfile(f):
+            return cls(default_crop * 256 // 224, default_crop)
+        cfg = json.load(open(f))
+        crop = cfg.get("crop_size", default_crop)
+        if isinstance(crop, dict):
+            if crop.get("height", default_crop) != crop.get("width", crop.get("height", default_crop)):
+                raise ValueError(f"Dinov2ImageProcessor: crop_size {crop} is not square (the tower takes one run size)")
+            crop = crop.get("height", default_crop)
+        size = cfg.get("size", crop * 256 // 224)
+        size = size.get("shortest_edge", size.get("height", crop)) if isinstance(size, dict) else size
+        return cls(size, crop, cfg.get("image_mean", IMAGENET_MEAN), cfg.get("image_std", IMAGENET_STD),
+                   cfg.get("rescale_factor", 1 / 255), cfg.get("resample", Image.BICUBIC))
+
+
 SIGLIP_MEAN = (0.5, 0.5, 0.5)
 SIGLIP_STD = (0.5, 0.5, 0.5)
 

@@ -8,18 +8,20 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import dataclasses
 import math
 import os
 import threading
 import weakref
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .weights import VisionConfig, SiglipVisionConfig, AdapterConfig, strip_tower_prefix, sub_state
+from .weights import VisionConfig, SiglipVisionConfig, Dinov2VisionConfig, AdapterConfig, strip_tower_prefix, strip_dinov2_prefix, sub_state
 
 LOG2E = 1.4426950408889634   # slime_attention takes q pre-scaled by head_dim^-0.5 * log2(e)
 
@@ -662,6 +664,218 @@ def siglip_tower_hidden_states(pt: PackedSiglipTower, pixels: torch.Tensor, k_sp
     states = torch.empty((pt.layers_run + 1, pixels.shape[0], pt.cfg.num_patches, pt.cfg.hidden_size), dtype=torch.float32,
                          device=pixels.device)
     _siglip_call(pt, pixels, None, None, states, k_split)
+    return states
+
+
+# ------------------------------------------------------------------------------------------------
+# DINOv2 towers (HF Dinov2Model / Dinov2WithRegistersModel, ViT-B/14 and ViT-L/14): slime_dinov2_forward
+# ------------------------------------------------------------------------------------------------
+DINOV2_ACT = "gelu"
+DINOV2_MAX_GRID = 24
+DINOV2_MAX_REGISTERS = 16
+DINOV2_WIDTHS = (128, 256, 768, 1024)
+
+
+@dataclass
+class PackedDinov2Tower:
+    cfg: Dinov2VisionConfig
+    dtype: torch.dtype
+    layers_run: int
+    tensors: Dict[str, torch.Tensor]
+    desc: _lib.VitDesc
+    ws: Workspace = field(default_factory=Workspace)
+
+    @property
+    def device(self):
+        return self.tensors["pos"].device
+
+
+def check_dinov2_config(cfg: Dinov2VisionConfig) -> None:
+    """The towers the DINOv2 path runs, refused by name otherwise (no device work): the plain MLP with the exact GELU, head_dim 64,
+    a width the kernels have, a run size of at most 24 whole patches per side that is a multiple of 8, at most 16 register tokens.
+    (The giant model: SwiGLU, head_dim 64 x 24 heads = 1536 wide; 518 px: 37 per side.)"""
+    if cfg.use_swiglu_ffn:
+        raise ValueError("DINOv2 vision tower use_swiglu_ffn=True (the giant model) is not supported: the HIP DINOv2 path runs the "
+                         "fc1 / GELU / fc2 MLP only")
+    if cfg.hidden_act != DINOV2_ACT:
+        raise ValueError(f"DINOv2 vision tower hidden_act={cfg.hidden_act!r} is not supported: the HIP DINOv2 path computes "
+                         f"{DINOV2_ACT!r} only")
+    if cfg.num_attention_heads <= 0 or cfg.hidden_size % cfg.num_attention_heads or cfg.head_dim != 64:
+        raise ValueError(f"DINOv2 vision tower head_dim={cfg.hidden_size / max(cfg.num_attention_heads, 1):g} (hidden_size {cfg.hidden_size} / "
+                         f"{cfg.num_attention_heads} heads) is not supported: head_dim must be 64")
+    if cfg.hidden_size not in DINOV2_WIDTHS:
+        raise ValueError(f"DINOv2 vision tower hidden_size={cfg.hidden_size} is not supported: the widths are "
+                         f"{', '.join(str(w) for w in DINOV2_WIDTHS)}")
+    if cfg.intermediate_size % 128:
+        raise ValueError(f"DINOv2 vision tower intermediate_size={cfg.intermediate_size} (hidden_size {cfg.hidden_size} x mlp_ratio "
+                         f"{cfg.mlp_ratio}) is not supported: it must be a multiple of 128")
+    if cfg.patch_size <= 0 or cfg.image_size <= 0 or cfg.image_size % cfg.patch_size or cfg.image_size % 8:
+        raise ValueError(f"DINOv2 vision tower run size {cfg.image_size} is not supported: it must be a multiple of patch_size "
+                         f"{cfg.patch_size} and of 8")
+    if cfg.grid > DINOV2_MAX_GRID:
+        raise ValueError(f"DINOv2 vision tower with {cfg.grid} patches per side (run size {cfg.image_size} / patch_size {cfg.patch_size}) "
+                         f"is not supported: at most {DINOV2_MAX_GRID} patches per side")
+    if not 0 <= cfg.num_register_tokens <= DINOV2_MAX_REGISTERS:
+        raise ValueError(f"DINOv2 vision tower num_register_tokens={cfg.num_register_tokens} is not supported: at most "
+                         f"{DINOV2_MAX_REGISTERS} register tokens")
+
+
+def dinov2_pos_table(pos: torch.Tensor, grid: int, antialias: bool) -> torch.Tensor:
+    """The patch rows of HF's ``interpolate_pos_encoding`` for a ``grid x grid`` input: ``pos`` [1, 1 + g0^2, D] -> fp32 [grid^2, D].
+    HF's own arguments (fp32, bicubic, align_corners=False, an explicit size; ``antialias`` only in Dinov2WithRegistersModel), and
+    as there no interpolation when the grids agree."""
+    patch = pos.detach().cpu()[0, 1:]
+    g0 = int(round(patch.shape[0] ** 0.5))
+    if g0 * g0 != patch.shape[0]:
+        raise ValueError(f"DINOv2 position table has {patch.shape[0]} patch rows: not a square grid")
+    if g0 == grid:
+        return patch.float().contiguous()
+    t = patch.reshape(1, g0, g0, -1).permute(0, 3, 1, 2).to(torch.float32)
+    t = torch.nn.functional.interpolate(t, size=(grid, grid), mode="bicubic", align_corners=False, antialias=antialias)
+    return t.permute(0, 2, 3, 1).reshape(grid * grid, -1).contiguous()
+
+
+def dinov2_host_tensors(state_dict: Dict[str, torch.Tensor], cfg: Dinov2VisionConfig, dtype: Optional[torch.dtype],
+                        select_layer: int = -2, image_size: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """``tower_host_tensors`` for the DINOv2 layout (``image_size``: the run size, default ``cfg.image_size``):
+      patch_w  the conv weight as a [D, kpad] matrix;
+      cls      the prefix table [n_prefix, D]: row 0 = cls_token + position 0, then the register tokens as they are;
+      pos      [P, D] = the position table's patch rows interpolated to the run grid (``dinov2_pos_table``) + the conv bias;
+      w_qkv / w_fc1 with norm1 / norm2 folded in (``fold_ln``), q rows carrying dh^-0.5 log2(e);
+      w_o = T(diag(lambda1) Wo), b_o = lambda1 * b and w_fc2 = T(diag(lambda2) W2), b_fc2 = lambda2 * b: LayerScale is linear.
+    Matrices in ``dtype``, everything else fp32; ``dtype=None``: nothing is rounded, every tensor float64 (the interpolation itself
+    is fp32 in HF whatever the model's dtype, and is here).  ``mask_token`` and ``layernorm.*`` are not read.
+
+    fp16 and small lambda: a folded weight lambda * w below 2^-14 lands on the fp16 subnormal grid (spacing 2^-24), so its absolute
+    rounding error is at most 2^-25 instead of 2^-11 relative; over a row of the GEMM that moves an element of h by at most
+    2^-25 * sum_k |a_k|.  bf16 has fp32's exponent range and keeps its relative 2^-8."""
+    if dtype not in (None, torch.bfloat16, torch.float16):
+        raise ValueError("tower compute dtype must be bf16 or fp16 (MFMA operand type); fp32 I/O is supported")
+    sd = strip_dinov2_prefix(state_dict)
+    if image_size is not None and image_size != cfg.image_size:
+        cfg = dataclasses.replace(cfg, image_size=int(image_size))
+    L = layers_for_select(cfg, select_layer)
+    f32, tt = _host_casts(dtype)
+    D, R, P2 = cfg.hidden_size, cfg.num_register_tokens, 3 * cfg.patch_size * cfg.patch_size
+    e = "embeddings."
+    pw = torch.zeros((D, (P2 + 63) // 64 * 64), dtype=torch.float32)
+    pw[:, :P2] = sd[e + "patch_embeddings.projection.weight"].detach().float().cpu().reshape(D, P2)
+    table = sd[e + "position_embeddings"]
+    prefix = [f32(sd[e + "cls_token"]).reshape(1, D) + f32(table)[0, :1]]
+    if R > 0:
+        regs = f32(sd[e + "register_tokens"]).reshape(-1, D)
+        if regs.shape[0] != R:
+            raise ValueError(f"DINOv2 checkpoint has {regs.shape[0]} register tokens, the config says {R}")
+        prefix.append(regs)
+    pos = f32(dinov2_pos_table(table, cfg.grid, cfg.antialias)) + f32(sd[e + "patch_embeddings.projection.bias"])[None, :]
+    T: Dict[str, torch.Tensor] = {"patch_w": tt(pw), "cls": torch.cat(prefix, 0).contiguous(), "pos": pos.contiguous()}
+    if L > 0:
+        rs = torch.ones(3 * D, dtype=torch.float64)
+        rs[:D] = cfg.head_dim ** -0.5 * LOG2E                  # q rows carry dh^-0.5 * log2 e (slime_attention contract)
+        cols = {k: [] for k in ("w_qkv", "b_qkv", "colsum_qkv", "w_fc1", "b_fc1", "colsum_fc1", "w_o", "b_o", "w_fc2", "b_fc2")}
+        for i in range(L):
+            q = f"encoder.layer.{i}."
+            a = q + "attention.attention."
+            Wm = torch.cat([sd[a + "query.weight"].float(), sd[a + "key.weight"].float(), sd[a + "value.weight"].float()], 0)
+            bm = torch.cat([sd[a + "query.bias"].float(), sd[a + "key.bias"].float(), sd[a + "value.bias"].float()], 0)
+            for k, v in zip(("w_qkv", "b_qkv", "colsum_qkv"), fold_ln(Wm, bm, sd[q + "norm1.weight"], sd[q + "norm1.bias"], rs, dtype)):
+                cols[k].append(v)
+            for k, v in zip(("w_fc1", "b_fc1", "colsum_fc1"),
+                            fold_ln(sd[q + "mlp.fc1.weight"], sd[q + "mlp.fc1.bias"], sd[q + "norm2.weight"], sd[q + "norm2.bias"], None, dtype)):
+                cols[k].append(v)
+            for w, b, lin, lam in (("w_o", "b_o", q + "attention.output.dense", q + "layer_scale1.lambda1"),
+                                   ("w_fc2", "b_fc2", q + "mlp.fc2", q + "layer_scale2.lambda1")):
+                s = sd[lam].detach().double().cpu()            # output feature j of the Linear is scaled by lambda[j]: row j of W, b[j]
+                cols[w].append(tt(sd[lin + ".weight"].detach().double().cpu() * s[:, None]))
+                cols[b].append(f32(sd[lin + ".bias"].detach().double().cpu() * s))
+        for k, v in cols.items():
+            T[k] = torch.stack(v).contiguous()
+    return T
+
+
+def pack_dinov2_tower(state_dict: Dict[str, torch.Tensor], cfg: Dinov2VisionConfig, dtype: torch.dtype, device,
+                      select_layer: int = -2, image_size: Optional[int] = None) -> PackedDinov2Tower:
+    """HF Dinov2Model / Dinov2WithRegistersModel state dict -> device tensors in the kernels' layout, as ``pack_tower``
+    (``dinov2_host_tensors`` on ``device``, the fragment-order images); slime_dinov2_check at pack time."""
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("tower compute dtype must be bf16 or fp16 (MFMA operand type); fp32 I/O is supported")
+    if image_size is not None and image_size != cfg.image_size:
+        cfg = dataclasses.replace(cfg, image_size=int(image_size))
+    check_dinov2_config(cfg)
+    L = layers_for_select(cfg, select_layer)
+    T: Dict[str, torch.Tensor] = {k: v.to(device).contiguous() for k, v in dinov2_host_tensors(state_dict, cfg, dtype, select_layer).items()}
+    if L > 0:
+        pack_static(T, ("w_qkv", "w_o", "w_fc1", "w_fc2"))
+    T["patch_w_frag"] = pack_b_frag(T["patch_w"])          # the front end (slime_patch_embed_prefix) reads this image only
+    if T["patch_w_frag"] is None:
+        if not T["patch_w"].is_cuda:
+            raise _lib.SlimeHipError("pack_dinov2_tower: weights are packed on the GPU (slime_gemm_pack_b): slime_amd has no CPU path")
+        raise ValueError("pack_dinov2_tower: the patch-embed weight could not be packed (hidden size must be a multiple of 64)")
+    T["patch_w"] = None
+    d = dinov2_desc(T, cfg, dtype, L)
+    _lib.check(_lib.load().slime_dinov2_check(C.byref(d), cfg.n_prefix), "pack_dinov2_tower")
+    return PackedDinov2Tower(cfg, dtype, L, T, d)
+
+
+def dinov2_desc(T: Dict[str, Optional[torch.Tensor]], cfg: Dinov2VisionConfig, dtype: torch.dtype, L: int) -> "_lib.VitDesc":
+    """slime_vit_desc of a DINOv2 tower: ``image`` is the run size, ``cls`` the prefix table, ``pre_ln_*`` stay NULL."""
+    return _vit_desc(T, SimpleNamespace(hidden_size=cfg.hidden_size, intermediate_size=cfg.intermediate_size,
+                                        num_attention_heads=cfg.num_attention_heads, image_size=cfg.image_size, patch_size=cfg.patch_size,
+                                        layer_norm_eps=cfg.layer_norm_eps), dtype, L)
+
+
+def _dinov2_pixels(pt: PackedDinov2Tower, pixels: torch.Tensor) -> torch.Tensor:
+    _require_cuda(pixels, "pixels")
+    s = pt.cfg.image_size
+    if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != s or pixels.shape[3] != s:
+        raise ValueError(f"Input image size ({tuple(pixels.shape[2:])}) doesn't match the size the tower was packed for ({s}*{s}).")
+    if pixels.dtype not in (torch.float32, pt.dtype):
+        pixels = pixels.to(pt.dtype)
+    return pixels.contiguous()
+
+
+def _dinov2_call(pt: PackedDinov2Tower, pixels, out, keep_prefix, hidden, states, k_split) -> None:
+    lib = _lib.load()
+    n, ks, npre = pixels.shape[0], None, pt.cfg.n_prefix
+    if k_split is not None:
+        if len(k_split) != 4:
+            raise ValueError("dinov2_tower_forward: k_split is (qkv, out_proj, fc1, fc2)")
+        ks = _lib.VitKsplit(*(int(v) for v in k_split))
+        need = lib.slime_dinov2_ksplit_workspace_bytes(C.byref(pt.desc), npre, n, C.byref(ks))
+    else:
+        need = lib.slime_dinov2_workspace_bytes(C.byref(pt.desc), npre, n)
+    base, avail = pt.ws.aligned(need, pixels.device)
+    _lib.check(lib.slime_dinov2_forward(C.byref(pt.desc), npre, pixels.data_ptr(), dtype_code(pixels.dtype), n, _ptr(out),
+                                        dtype_code(out.dtype) if out is not None else _lib.F32, int(bool(keep_prefix)), _ptr(hidden),
+                                        _ptr(states), C.byref(ks) if ks is not None else None, base, avail, _stream()),
+               "slime_dinov2_forward")
+
+
+def dinov2_tower_forward(pt: PackedDinov2Tower, pixels: torch.Tensor, out_dtype: Optional[torch.dtype] = None,
+                         keep_prefix: bool = False, want_hidden: bool = False, out: Optional[torch.Tensor] = None,
+                         k_split: Optional[Sequence[int]] = None):
+    """pixels [N,3,S,S] (fp32 or the tower dtype) -> hidden_states[select_layer] in out_dtype: the P patch rows [N, P, D], or with
+    ``keep_prefix`` all n_prefix + P rows (class token, registers, patches).  ``want_hidden`` adds the fp32 state with all rows.
+    k_split as in :func:`tower_forward`."""
+    pixels = _dinov2_pixels(pt, pixels)
+    cfg, n = pt.cfg, pixels.shape[0]
+    out_dtype = out_dtype or pixels.dtype
+    rows = cfg.seq_len if keep_prefix else cfg.num_patches
+    if out is None:
+        out = torch.empty((n, rows, cfg.hidden_size), dtype=out_dtype, device=pixels.device)
+    elif tuple(out.shape) != (n, rows, cfg.hidden_size) or out.dtype != out_dtype or not out.is_contiguous():
+        raise ValueError("dinov2_tower_forward: out must be a contiguous [N, rows, hidden] tensor of the output dtype")
+    hidden = torch.empty((n, cfg.seq_len, cfg.hidden_size), dtype=torch.float32, device=pixels.device) if want_hidden else None
+    _dinov2_call(pt, pixels, out, keep_prefix, hidden, None, k_split)
+    return (out, hidden) if want_hidden else out
+
+
+def dinov2_tower_hidden_states(pt: PackedDinov2Tower, pixels: torch.Tensor, k_split: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """pixels [N,3,S,S] -> fp32 [layers_run + 1, N, n_prefix + P, D]: HF's hidden_states of ONE tower pass (entry 0 = the embeddings)."""
+    pixels = _dinov2_pixels(pt, pixels)
+    states = torch.empty((pt.layers_run + 1, pixels.shape[0], pt.cfg.seq_len, pt.cfg.hidden_size), dtype=torch.float32,
+                         device=pixels.device)
+    _dinov2_call(pt, pixels, None, True, None, states, k_split)
     return states
 
 

@@ -209,6 +209,119 @@ def make_siglip_state_dict(cfg: SiglipVisionConfig = SIGLIP_L_384, seed: int = 1
     return sd
 
 
+@dataclass(frozen=True)
+class Dinov2VisionConfig:
+    """Geometry of a DINOv2 vision tower (HF ``Dinov2Config`` / ``Dinov2WithRegistersConfig`` field names; defaults: ViT-L/14 without
+    registers).  ``image_size`` is the size the tower RUNS at, as for every tower config of this package (224: the released
+    checkpoints' ``crop_size``); ``table_grid`` is the grid the position table was made for (HF's ``image_size`` 518 / 14 = 37 in
+    the released checkpoints): the table is interpolated to the run grid once, at pack time.  A crop is
+    ``[cls] [num_register_tokens registers] [num_patches patches]``: ``n_prefix`` rows in front of the patches."""
+    hidden_size: int = 1024
+    num_hidden_layers: int = 24
+    num_attention_heads: int = 16
+    mlp_ratio: int = 4
+    image_size: int = 224
+    patch_size: int = 14
+    layer_norm_eps: float = 1e-6
+    hidden_act: str = "gelu"
+    table_grid: int = 37
+    use_swiglu_ffn: bool = False
+    num_register_tokens: int = 0
+    model_type: str = "dinov2"            # or "dinov2_with_registers": HF interpolates the position table with antialias=True there
+
+    @property
+    def intermediate_size(self) -> int:
+        return int(self.hidden_size * self.mlp_ratio)
+
+    @property
+    def grid(self) -> int:
+        return self.image_size // self.patch_size
+
+    @property
+    def num_patches(self) -> int:
+        return self.grid * self.grid
+
+    @property
+    def n_prefix(self) -> int:
+        return 1 + self.num_register_tokens
+
+    @property
+    def seq_len(self) -> int:
+        return self.n_prefix + self.num_patches
+
+    @property
+    def head_dim(self) -> int:
+        return self.hidden_size // self.num_attention_heads
+
+    @property
+    def antialias(self) -> bool:
+        return self.model_type == "dinov2_with_registers"
+
+    def to_dict(self):
+        return asdict(self)
+
+
+DINOV2_L_224 = Dinov2VisionConfig()
+DINOV2_L_REG4_224 = Dinov2VisionConfig(num_register_tokens=4, model_type="dinov2_with_registers")
+
+
+def make_dinov2_state_dict(cfg: Dinov2VisionConfig = DINOV2_L_224, seed: int = 1234) -> Dict[str, torch.Tensor]:
+    """fp32 state dict with HF ``Dinov2Model`` / ``Dinov2WithRegistersModel`` key names (no prefix, as HF saves them): class, mask
+    and register tokens, a position table of 1 + table_grid^2 rows, a conv with bias, per layer norm1 / attention / LayerScale /
+    norm2 / MLP / LayerScale, the final ``layernorm`` (part of a checkpoint, never run here).  Scales as in
+    :func:`make_tower_state_dict`; the LayerScale lambdas are log-uniform in [1e-4, 1] (the released checkpoints train them from
+    1.0 and reach both ends of that range)."""
+    g = _gen(seed)
+    D, F, P, R = cfg.hidden_size, cfg.intermediate_size, cfg.patch_size, cfg.num_register_tokens
+    sd: Dict[str, torch.Tensor] = {}
+    e = "embeddings."
+    sd[e + "cls_token"] = _normal(g, (1, 1, D), D ** -0.5)
+    sd[e + "mask_token"] = _normal(g, (1, D), 0.02)
+    if R > 0:
+        sd[e + "register_tokens"] = _normal(g, (1, R, D), D ** -0.5)
+    sd[e + "position_embeddings"] = _normal(g, (1, 1 + cfg.table_grid ** 2, D), 0.02)
+    sd[e + "patch_embeddings.projection.weight"] = _normal(g, (D, 3, P, P), 0.02)
+    sd[e + "patch_embeddings.projection.bias"] = _normal(g, (D,), 0.05)
+    depth_scale = (2 * cfg.num_hidden_layers) ** -0.5
+
+    def lam():
+        return torch.exp(torch.rand((D,), generator=g, dtype=torch.float32) * math.log(1e-4))
+
+    for i in range(cfg.num_hidden_layers):
+        q = f"encoder.layer.{i}."
+        sd[q + "norm1.weight"] = _normal(g, (D,), 0.1, 1.0)
+        sd[q + "norm1.bias"] = _normal(g, (D,), 0.05)
+        for name, std in (("attention.attention.query", D ** -0.5), ("attention.attention.key", D ** -0.5),
+                          ("attention.attention.value", D ** -0.5), ("attention.output.dense", D ** -0.5 * depth_scale * 2.0)):
+            sd[q + f"{name}.weight"] = _normal(g, (D, D), std)
+            sd[q + f"{name}.bias"] = _normal(g, (D,), 0.02)
+        sd[q + "layer_scale1.lambda1"] = lam()
+        sd[q + "norm2.weight"] = _normal(g, (D,), 0.1, 1.0)
+        sd[q + "norm2.bias"] = _normal(g, (D,), 0.05)
+        sd[q + "mlp.fc1.weight"] = _normal(g, (F, D), (2 * D) ** -0.5 * 2.0)
+        sd[q + "mlp.fc1.bias"] = _normal(g, (F,), 0.02)
+        sd[q + "mlp.fc2.weight"] = _normal(g, (D, F), F ** -0.5 * depth_scale * 2.0)
+        sd[q + "mlp.fc2.bias"] = _normal(g, (D,), 0.02)
+        sd[q + "layer_scale2.lambda1"] = lam()
+    sd["layernorm.weight"] = _normal(g, (D,), 0.1, 1.0)
+    sd["layernorm.bias"] = _normal(g, (D,), 0.05)
+    return sd
+
+
+DINOV2_KEY_PREFIXES = ("dinov2_with_registers.", "dinov2.", "vision_model.", "backbone.")
+
+
+def strip_dinov2_prefix(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """HF saves a bare ``Dinov2Model`` without a prefix; a model that wraps it (classification, backbone, this package's parameter
+    container) prefixes every key with the attribute that holds it.  Both are accepted."""
+    def bare(k: str) -> str:
+        for p in DINOV2_KEY_PREFIXES:
+            if k.startswith(p):
+                return bare(k[len(p):])
+        return k
+    return {bare(k): v for k, v in sd.items()}
+
+
 def canonical_tower_key(key: str) -> str:
     """Map either HF naming generation onto the prefix-free form used internally."""
     return key[len("vision_model."):] if key.startswith("vision_model.") else key
