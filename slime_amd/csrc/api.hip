@@ -70,14 +70,21 @@ struct VitPlan {
 // The three tower forms the layer loop serves (vit_run): the CLIP layout (class token + pre-LayerNorm, S = P + 1 rows per crop), the
 // plain one of the SigLIP towers (S = P rows behind slime_patch_embed_plain, fc1 with the tanh-form GELU) and the prefix one of the
 // DINOv2 towers (n_prefix > 0: S = n_prefix + P rows behind slime_patch_embed_prefix, no pre-LayerNorm, fc1 with the exact GELU).
-struct VitForm { bool plain; int fc1_epilogue; int n_prefix = 0; };
-static int vit_seq(const slime_vit_desc* d, bool plain, int n_prefix = 0) {
+// `lead` = the rows in front of a crop's patches: the class token, none, the n_prefix table rows.
+struct VitForm { bool plain; int fc1_epilogue; int n_prefix; int lead; };
+static VitForm clip_form(int act = SLIME_ACT_QUICKGELU) {
+    return {false, act == SLIME_ACT_GELU ? SLIME_EPI_BIAS_GELU_T : SLIME_EPI_BIAS_QUICKGELU_T, 0, 1};
+}
+static VitForm siglip_form() { return {true, SLIME_EPI_BIAS_GELU_TANH_T, 0, 0}; }
+static VitForm dinov2_form(int n_prefix) { return {false, SLIME_EPI_BIAS_GELU_T, n_prefix, n_prefix}; }
+
+static int vit_seq(const slime_vit_desc* d, const VitForm& form) {
     const int g = d->image / d->patch;
-    return g * g + (n_prefix > 0 ? n_prefix : plain ? 0 : 1);
+    return g * g + form.lead;
 }
 
-static VitPlan vit_plan(const slime_vit_desc* d, int n, bool plain = false, int n_prefix = 0) {
-    const int S = vit_seq(d, plain, n_prefix);
+static VitPlan vit_plan(const slime_vit_desc* d, int n, const VitForm& form) {
+    const int S = vit_seq(d, form);
     const size_t M = (size_t)n * S, D = d->hidden;
     VitPlan p{};
     size_t off = 0;
@@ -101,13 +108,13 @@ static VitPlan vit_plan(const slime_vit_desc* d, int n, bool plain = false, int 
 
 int slime_patch_embed_geometry(int image, int patch, int kpad, int D, size_t* lds_out);   // patch_embed.hip: the fused front end's limits
 
-static int vit_validate(const slime_vit_desc* d, bool plain = false, int n_prefix = 0) {
+static int vit_validate(const slime_vit_desc* d, const VitForm& form) {
     SLIME_REQUIRE(d, "vit: null descriptor");
-    if (n_prefix > 0) {                             // the DINOv2 entries: cls carries the prefix table, the pre-LayerNorm fields stay empty
+    if (form.n_prefix > 0) {                             // the DINOv2 entries: cls carries the prefix table, the pre-LayerNorm fields stay empty
         SLIME_REQUIRE(d->cls, "dinov2: cls is required (the prefix table [n_prefix, hidden]: class token + position 0, then the register tokens)");
         SLIME_REQUIRE(!d->pre_ln_w, "dinov2: pre_ln_w must be NULL (a DINOv2 tower has no pre-LayerNorm)");
         SLIME_REQUIRE(!d->pre_ln_b, "dinov2: pre_ln_b must be NULL (a DINOv2 tower has no pre-LayerNorm)");
-    } else if (plain) {                                    // the SigLIP entries: the descriptor's class-token / pre-LayerNorm fields stay empty
+    } else if (form.plain) {                                    // the SigLIP entries: the descriptor's class-token / pre-LayerNorm fields stay empty
         SLIME_REQUIRE(!d->cls, "siglip: cls must be NULL (a SigLIP tower has no class token; slime_vit_forward* run the CLIP layout)");
         SLIME_REQUIRE(!d->pre_ln_w, "siglip: pre_ln_w must be NULL (a SigLIP tower has no pre-LayerNorm)");
         SLIME_REQUIRE(!d->pre_ln_b, "siglip: pre_ln_b must be NULL (a SigLIP tower has no pre-LayerNorm)");
@@ -120,7 +127,7 @@ static int vit_validate(const slime_vit_desc* d, bool plain = false, int n_prefi
     SLIME_REQUIRE(d->patch > 0 && d->image % d->patch == 0, "vit: image %d not a multiple of patch %d", d->image, d->patch);
     TRY(slime_patch_embed_geometry(d->image, d->patch, d->kpad, d->hidden, nullptr));      // the one-launch front end's geometry limits
     SLIME_REQUIRE(d->layers_run >= 0, "vit: layers_run < 0");
-    SLIME_REQUIRE(d->patch_w_frag && d->pos && (plain || n_prefix > 0 || (d->cls && d->pre_ln_w && d->pre_ln_b)),
+    SLIME_REQUIRE(d->patch_w_frag && d->pos && (form.plain || form.n_prefix > 0 || (d->cls && d->pre_ln_w && d->pre_ln_b)),
                   "vit: missing embedding weights (patch_w_frag = slime_gemm_pack_b of the conv weight is required since ABI 5)");
     // a per-layer weight is given as its fragment-order image, its row-major image, or both (slime_gemm_b_frag_usable)
     SLIME_REQUIRE(d->layers_run == 0 || ((d->w_qkv || d->w_qkv_frag) && d->b_qkv && d->colsum_qkv && (d->w_o || d->w_o_frag) && d->b_o &&
@@ -129,19 +136,25 @@ static int vit_validate(const slime_vit_desc* d, bool plain = false, int n_prefi
     return SLIME_OK;
 }
 
-extern "C" int slime_vit_check(const slime_vit_desc* d) { return vit_validate(d); }
-
-extern "C" int slime_vit_residual_epilogue(void) { return SLIME_EPI_BIAS_RESID_SPLIT_LN; }
-
-extern "C" size_t slime_vit_workspace_bytes(const slime_vit_desc* d, int n_crops) {
-    if (!d || n_crops <= 0 || d->patch <= 0) return 0;
-    return vit_plan(d, n_crops).total;
+// splits per layer GEMM (slime_vit_forward_ksplit): each within its GEMM's range -- 1..SLIME_GEMM_KSPLIT_MAX and at most K / 64
+static int vit_ksplit_validate(const slime_vit_desc* d, const slime_vit_ksplit* ks) {
+    const int kmax_d = d->hidden / 64 < SLIME_GEMM_KSPLIT_MAX ? d->hidden / 64 : SLIME_GEMM_KSPLIT_MAX;
+    const int kmax_f = d->inter / 64 < SLIME_GEMM_KSPLIT_MAX ? d->inter / 64 : SLIME_GEMM_KSPLIT_MAX;
+    SLIME_REQUIRE(ks->qkv >= 1 && ks->qkv <= kmax_d, "vit: k-split qkv=%d outside 1..%d (K = hidden = %d)", ks->qkv, kmax_d, d->hidden);
+    SLIME_REQUIRE(ks->out_proj >= 1 && ks->out_proj <= kmax_d, "vit: k-split out_proj=%d outside 1..%d (K = hidden = %d)", ks->out_proj, kmax_d, d->hidden);
+    SLIME_REQUIRE(ks->fc1 >= 1 && ks->fc1 <= kmax_d, "vit: k-split fc1=%d outside 1..%d (K = hidden = %d)", ks->fc1, kmax_d, d->hidden);
+    SLIME_REQUIRE(ks->fc2 >= 1 && ks->fc2 <= kmax_f, "vit: k-split fc2=%d outside 1..%d (K = intermediate = %d)", ks->fc2, kmax_f, d->inter);
+    return SLIME_OK;
 }
 
-extern "C" int slime_vit_forward(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out,
-                                 int out_dtype, int keep_cls, float* hidden_f32, void* ws, size_t ws_bytes,
-                                 void* stream) {
-    return slime_vit_forward_ex(d, pixels, pix_dtype, n, out, out_dtype, keep_cls, hidden_f32, ws, ws_bytes, stream, nullptr);
+static size_t vit_ksplit_partial_bytes(const slime_vit_desc* d, int n, const slime_vit_ksplit* ks, const VitForm& form) {
+    const int M = n * vit_seq(d, form);
+    size_t b = slime_gemm_ksplit_workspace_bytes(M, 3 * d->hidden, ks->qkv);
+    auto grow = [&](size_t x) { if (x > b) b = x; };
+    grow(slime_gemm_ksplit_workspace_bytes(M, d->hidden, ks->out_proj));
+    grow(slime_gemm_ksplit_workspace_bytes(M, d->inter, ks->fc1));
+    grow(slime_gemm_ksplit_workspace_bytes(M, d->hidden, ks->fc2));
+    return b;
 }
 
 // diagnostic build only (libslime_hip_diag.so; results become wrong): bit k set = the tower skips kernel id k of every layer, to read each kernel's
@@ -163,122 +176,14 @@ static constexpr int g_vit_skip_mask = 0;
 
 static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out, int out_dtype, int keep_cls,
                    float* hidden_f32, void* ws, size_t ws_bytes, void* stream, const slime_probe* probe, float* states,
-                   const slime_vit_ksplit* ks = nullptr, VitForm form = VitForm{false, SLIME_EPI_BIAS_QUICKGELU_T});
-
-extern "C" int slime_vit_forward_ex(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out,
-                                    int out_dtype, int keep_cls, float* hidden_f32, void* ws, size_t ws_bytes,
-                                    void* stream, const slime_probe* probe) {
-    return vit_run(d, pixels, pix_dtype, n, out, out_dtype, keep_cls, hidden_f32, ws, ws_bytes, stream, probe, nullptr);
-}
-
-// splits per layer GEMM (slime_vit_forward_ksplit): each within its GEMM's range -- 1..SLIME_GEMM_KSPLIT_MAX and at most K / 64
-static int vit_ksplit_validate(const slime_vit_desc* d, const slime_vit_ksplit* ks) {
-    const int kmax_d = d->hidden / 64 < SLIME_GEMM_KSPLIT_MAX ? d->hidden / 64 : SLIME_GEMM_KSPLIT_MAX;
-    const int kmax_f = d->inter / 64 < SLIME_GEMM_KSPLIT_MAX ? d->inter / 64 : SLIME_GEMM_KSPLIT_MAX;
-    SLIME_REQUIRE(ks->qkv >= 1 && ks->qkv <= kmax_d, "vit: k-split qkv=%d outside 1..%d (K = hidden = %d)", ks->qkv, kmax_d, d->hidden);
-    SLIME_REQUIRE(ks->out_proj >= 1 && ks->out_proj <= kmax_d, "vit: k-split out_proj=%d outside 1..%d (K = hidden = %d)", ks->out_proj, kmax_d, d->hidden);
-    SLIME_REQUIRE(ks->fc1 >= 1 && ks->fc1 <= kmax_d, "vit: k-split fc1=%d outside 1..%d (K = hidden = %d)", ks->fc1, kmax_d, d->hidden);
-    SLIME_REQUIRE(ks->fc2 >= 1 && ks->fc2 <= kmax_f, "vit: k-split fc2=%d outside 1..%d (K = intermediate = %d)", ks->fc2, kmax_f, d->inter);
-    return SLIME_OK;
-}
-
-static size_t vit_ksplit_partial_bytes(const slime_vit_desc* d, int n, const slime_vit_ksplit* ks, bool plain = false, int n_prefix = 0) {
-    const int M = n * vit_seq(d, plain, n_prefix);
-    size_t b = slime_gemm_ksplit_workspace_bytes(M, 3 * d->hidden, ks->qkv);
-    auto grow = [&](size_t x) { if (x > b) b = x; };
-    grow(slime_gemm_ksplit_workspace_bytes(M, d->hidden, ks->out_proj));
-    grow(slime_gemm_ksplit_workspace_bytes(M, d->inter, ks->fc1));
-    grow(slime_gemm_ksplit_workspace_bytes(M, d->hidden, ks->fc2));
-    return b;
-}
-
-extern "C" size_t slime_vit_ksplit_workspace_bytes(const slime_vit_desc* d, int n_crops, const slime_vit_ksplit* ks) {
-    if (!d || !ks || n_crops <= 0 || d->patch <= 0) return 0;
-    return vit_plan(d, n_crops).total + vit_ksplit_partial_bytes(d, n_crops, ks);
-}
-
-extern "C" int slime_vit_forward_ksplit(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out, int out_dtype,
-                                        int keep_cls, float* hidden_f32, const slime_vit_ksplit* ks, void* ws, size_t ws_bytes, void* stream) {
-    SLIME_REQUIRE(ks, "vit_forward_ksplit: null k-split setting (slime_vit_forward is the unsplit call)");
-    return vit_run(d, pixels, pix_dtype, n, out, out_dtype, keep_cls, hidden_f32, ws, ws_bytes, stream, nullptr, nullptr, ks);
-}
-
-extern "C" int slime_vit_forward_states(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, float* states_f32,
-                                        void* ws, size_t ws_bytes, void* stream) {
-    SLIME_REQUIRE(states_f32, "vit_forward_states: states_f32 is required");
-    return vit_run(d, pixels, pix_dtype, n, nullptr, SLIME_F32, 1, nullptr, ws, ws_bytes, stream, nullptr, states_f32);
-}
-
-// The superset of slime_vit_forward / _ksplit / _states, with the options a descriptor does not carry (the MLP's activation).
-extern "C" int slime_vit_forward_opts(const slime_vit_desc* d, const slime_vit_opts* opts, const void* pixels, int pix_dtype, int n,
-                                      void* out, int out_dtype, int keep_cls, float* hidden_f32, float* states_f32,
-                                      const slime_vit_ksplit* ks, void* ws, size_t ws_bytes, void* stream) {
-    const int act = opts ? opts->act : SLIME_ACT_QUICKGELU;
-    SLIME_REQUIRE(act == SLIME_ACT_QUICKGELU || act == SLIME_ACT_GELU, "vit_forward_opts: act=%d is neither SLIME_ACT_QUICKGELU (0) nor "
-                                                                       "SLIME_ACT_GELU (1)", act);
-    return vit_run(d, pixels, pix_dtype, n, out, out_dtype, keep_cls, hidden_f32, ws, ws_bytes, stream, nullptr, states_f32, ks,
-                   VitForm{false, act == SLIME_ACT_GELU ? SLIME_EPI_BIAS_GELU_T : SLIME_EPI_BIAS_QUICKGELU_T});
-}
-
-// SigLIP towers: vit_run's layer loop in its plain form (include/slime_hip.h)
-extern "C" int slime_siglip_check(const slime_vit_desc* d) { return vit_validate(d, true); }
-
-extern "C" size_t slime_siglip_workspace_bytes(const slime_vit_desc* d, int n_crops) {
-    if (!d || n_crops <= 0 || d->patch <= 0) return 0;
-    return vit_plan(d, n_crops, true).total;
-}
-
-extern "C" size_t slime_siglip_ksplit_workspace_bytes(const slime_vit_desc* d, int n_crops, const slime_vit_ksplit* ks) {
-    if (!d || !ks || n_crops <= 0 || d->patch <= 0) return 0;
-    return vit_plan(d, n_crops, true).total + vit_ksplit_partial_bytes(d, n_crops, ks, true);
-}
-
-extern "C" int slime_siglip_forward(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out, int out_dtype,
-                                    float* hidden_f32, float* states_f32, const slime_vit_ksplit* ks, void* ws, size_t ws_bytes,
-                                    void* stream) {
-    return vit_run(d, pixels, pix_dtype, n, out, out_dtype, 1, hidden_f32, ws, ws_bytes, stream, nullptr, states_f32, ks,
-                   VitForm{true, SLIME_EPI_BIAS_GELU_TANH_T});
-}
-
-// DINOv2 towers: vit_run's layer loop in its prefix form (include/slime_hip.h)
-static int dinov2_prefix_ok(int n_prefix) {
-    SLIME_REQUIRE(n_prefix >= 1 && n_prefix <= 17, "dinov2: n_prefix=%d outside 1..17 (the class token and at most 16 register tokens)", n_prefix);
-    return SLIME_OK;
-}
-
-extern "C" int slime_dinov2_check(const slime_vit_desc* d, int n_prefix) {
-    TRY(dinov2_prefix_ok(n_prefix));
-    return vit_validate(d, false, n_prefix);
-}
-
-extern "C" size_t slime_dinov2_workspace_bytes(const slime_vit_desc* d, int n_prefix, int n_crops) {
-    if (!d || n_crops <= 0 || d->patch <= 0 || n_prefix < 1 || n_prefix > 17) return 0;
-    return vit_plan(d, n_crops, false, n_prefix).total;
-}
-
-extern "C" size_t slime_dinov2_ksplit_workspace_bytes(const slime_vit_desc* d, int n_prefix, int n_crops, const slime_vit_ksplit* ks) {
-    if (!d || !ks || n_crops <= 0 || d->patch <= 0 || n_prefix < 1 || n_prefix > 17) return 0;
-    return vit_plan(d, n_crops, false, n_prefix).total + vit_ksplit_partial_bytes(d, n_crops, ks, false, n_prefix);
-}
-
-extern "C" int slime_dinov2_forward(const slime_vit_desc* d, int n_prefix, const void* pixels, int pix_dtype, int n, void* out, int out_dtype,
-                                    int keep_prefix, float* hidden_f32, float* states_f32, const slime_vit_ksplit* ks, void* ws,
-                                    size_t ws_bytes, void* stream) {
-    TRY(dinov2_prefix_ok(n_prefix));
-    return vit_run(d, pixels, pix_dtype, n, out, out_dtype, keep_prefix, hidden_f32, ws, ws_bytes, stream, nullptr, states_f32, ks,
-                   VitForm{false, SLIME_EPI_BIAS_GELU_T, n_prefix});
-}
-
-static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out, int out_dtype, int keep_cls,
-                   float* hidden_f32, void* ws, size_t ws_bytes, void* stream, const slime_probe* probe, float* states,
-                   const slime_vit_ksplit* ks, VitForm form) {
-    TRY(vit_validate(d, form.plain, form.n_prefix));
+                   const slime_vit_ksplit* ks, const VitForm& form) {
+    TRY(vit_validate(d, form));
     SLIME_REQUIRE(pixels && n > 0, "vit: bad input");
     SLIME_REQUIRE(out || hidden_f32 || states, "vit: no output requested");
     SLIME_REQUIRE(!out || out_dtype == SLIME_F32 || is16(out_dtype), "vit: bad out dtype");
     if (ks) TRY(vit_ksplit_validate(d, ks));
-    const VitPlan p = vit_plan(d, n, form.plain, form.n_prefix);
-    const size_t part_bytes = ks ? vit_ksplit_partial_bytes(d, n, ks, form.plain, form.n_prefix) : 0;      // one region of partial products behind the plan
+    const VitPlan p = vit_plan(d, n, form);
+    const size_t part_bytes = ks ? vit_ksplit_partial_bytes(d, n, ks, form) : 0;      // one region of partial products behind the plan
     TRY(ws_check("vit", ws, ws_bytes, p.total + part_bytes));
     // a layer GEMM: slime_gemm_ex, or the split pair where the caller asked for one (the probe brackets the GEMM as a whole)
     auto layer_gemm = [&](const slime_gemm_args& a, int splits) {
@@ -286,7 +191,7 @@ static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, i
     };
     const slime_vit_ksplit k1{1, 1, 1, 1};
     const slime_vit_ksplit& sp = ks ? *ks : k1;
-    const int S = vit_seq(d, form.plain, form.n_prefix), lead = form.n_prefix > 0 ? form.n_prefix : form.plain ? 0 : 1;   // rows before the patches
+    const int S = vit_seq(d, form), lead = form.lead;
     const int P = S - lead, D = d->hidden, F = d->inter;
     const int M = n * S;
     char* w = (char*)ws;
@@ -367,12 +272,105 @@ static int vit_run(const slime_vit_desc* d, const void* pixels, int pix_dtype, i
     }
     if (hidden_f32) TRY(slime_gather_rows_split(xn, lo, dt, S, 0, hidden_f32, SLIME_F32, n, S, D, stream));
     if (out) {
-        // feature_select: 'patch' drops the class token (clip_encoder.py:38-39), cast to out dtype (:52,56); the plain form has none:
-        // all S = P rows; the prefix form drops its n_prefix rows (keep_prefix = 0) or none
-        const bool all_rows = keep_cls || form.plain;
-        TRY(slime_gather_rows_split(xn, lo, dt, S, all_rows ? 0 : lead, out, out_dtype, n, all_rows ? S : P, D, stream));
+        // feature_select: 'patch' drops the class token (clip_encoder.py:38-39), cast to out dtype (:52,56); the plain form has none
+        // (lead = 0: all S = P rows either way); the prefix form drops its n_prefix rows (keep_prefix = 0) or none
+        TRY(slime_gather_rows_split(xn, lo, dt, S, keep_cls ? 0 : lead, out, out_dtype, n, keep_cls ? S : P, D, stream));
     }
     return SLIME_OK;
+}
+
+// what the six *_workspace_bytes entries return: the plan, plus the region of partial products where the pass is split (ks)
+static size_t vit_workspace(const slime_vit_desc* d, int n_crops, const slime_vit_ksplit* ks, const VitForm& form) {
+    if (!d || n_crops <= 0 || d->patch <= 0) return 0;
+    return vit_plan(d, n_crops, form).total + (ks ? vit_ksplit_partial_bytes(d, n_crops, ks, form) : 0);
+}
+
+extern "C" int slime_vit_check(const slime_vit_desc* d) { return vit_validate(d, clip_form()); }
+
+extern "C" int slime_vit_residual_epilogue(void) { return SLIME_EPI_BIAS_RESID_SPLIT_LN; }
+
+extern "C" size_t slime_vit_workspace_bytes(const slime_vit_desc* d, int n_crops) { return vit_workspace(d, n_crops, nullptr, clip_form()); }
+
+extern "C" int slime_vit_forward(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out,
+                                 int out_dtype, int keep_cls, float* hidden_f32, void* ws, size_t ws_bytes,
+                                 void* stream) {
+    return slime_vit_forward_ex(d, pixels, pix_dtype, n, out, out_dtype, keep_cls, hidden_f32, ws, ws_bytes, stream, nullptr);
+}
+
+extern "C" int slime_vit_forward_ex(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out,
+                                    int out_dtype, int keep_cls, float* hidden_f32, void* ws, size_t ws_bytes,
+                                    void* stream, const slime_probe* probe) {
+    return vit_run(d, pixels, pix_dtype, n, out, out_dtype, keep_cls, hidden_f32, ws, ws_bytes, stream, probe, nullptr, nullptr, clip_form());
+}
+
+extern "C" size_t slime_vit_ksplit_workspace_bytes(const slime_vit_desc* d, int n_crops, const slime_vit_ksplit* ks) {
+    return ks ? vit_workspace(d, n_crops, ks, clip_form()) : 0;
+}
+
+extern "C" int slime_vit_forward_ksplit(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out, int out_dtype,
+                                        int keep_cls, float* hidden_f32, const slime_vit_ksplit* ks, void* ws, size_t ws_bytes, void* stream) {
+    SLIME_REQUIRE(ks, "vit_forward_ksplit: null k-split setting (slime_vit_forward is the unsplit call)");
+    return vit_run(d, pixels, pix_dtype, n, out, out_dtype, keep_cls, hidden_f32, ws, ws_bytes, stream, nullptr, nullptr, ks, clip_form());
+}
+
+extern "C" int slime_vit_forward_states(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, float* states_f32,
+                                        void* ws, size_t ws_bytes, void* stream) {
+    SLIME_REQUIRE(states_f32, "vit_forward_states: states_f32 is required");
+    return vit_run(d, pixels, pix_dtype, n, nullptr, SLIME_F32, 1, nullptr, ws, ws_bytes, stream, nullptr, states_f32, nullptr, clip_form());
+}
+
+// The superset of slime_vit_forward / _ksplit / _states, with the options a descriptor does not carry (the MLP's activation).
+extern "C" int slime_vit_forward_opts(const slime_vit_desc* d, const slime_vit_opts* opts, const void* pixels, int pix_dtype, int n,
+                                      void* out, int out_dtype, int keep_cls, float* hidden_f32, float* states_f32,
+                                      const slime_vit_ksplit* ks, void* ws, size_t ws_bytes, void* stream) {
+    const int act = opts ? opts->act : SLIME_ACT_QUICKGELU;
+    SLIME_REQUIRE(act == SLIME_ACT_QUICKGELU || act == SLIME_ACT_GELU, "vit_forward_opts: act=%d is neither SLIME_ACT_QUICKGELU (0) nor "
+                                                                       "SLIME_ACT_GELU (1)", act);
+    return vit_run(d, pixels, pix_dtype, n, out, out_dtype, keep_cls, hidden_f32, ws, ws_bytes, stream, nullptr, states_f32, ks,
+                   clip_form(act));
+}
+
+// SigLIP towers: vit_run's layer loop in its plain form (include/slime_hip.h)
+extern "C" int slime_siglip_check(const slime_vit_desc* d) { return vit_validate(d, siglip_form()); }
+
+extern "C" size_t slime_siglip_workspace_bytes(const slime_vit_desc* d, int n_crops) { return vit_workspace(d, n_crops, nullptr, siglip_form()); }
+
+extern "C" size_t slime_siglip_ksplit_workspace_bytes(const slime_vit_desc* d, int n_crops, const slime_vit_ksplit* ks) {
+    return ks ? vit_workspace(d, n_crops, ks, siglip_form()) : 0;
+}
+
+extern "C" int slime_siglip_forward(const slime_vit_desc* d, const void* pixels, int pix_dtype, int n, void* out, int out_dtype,
+                                    float* hidden_f32, float* states_f32, const slime_vit_ksplit* ks, void* ws, size_t ws_bytes,
+                                    void* stream) {
+    return vit_run(d, pixels, pix_dtype, n, out, out_dtype, 1, hidden_f32, ws, ws_bytes, stream, nullptr, states_f32, ks,
+                   siglip_form());
+}
+
+// DINOv2 towers: vit_run's layer loop in its prefix form (include/slime_hip.h)
+static int dinov2_prefix_ok(int n_prefix) {
+    SLIME_REQUIRE(n_prefix >= 1 && n_prefix <= 17, "dinov2: n_prefix=%d outside 1..17 (the class token and at most 16 register tokens)", n_prefix);
+    return SLIME_OK;
+}
+
+extern "C" int slime_dinov2_check(const slime_vit_desc* d, int n_prefix) {
+    TRY(dinov2_prefix_ok(n_prefix));
+    return vit_validate(d, dinov2_form(n_prefix));
+}
+
+extern "C" size_t slime_dinov2_workspace_bytes(const slime_vit_desc* d, int n_prefix, int n_crops) {
+    return n_prefix >= 1 && n_prefix <= 17 ? vit_workspace(d, n_crops, nullptr, dinov2_form(n_prefix)) : 0;
+}
+
+extern "C" size_t slime_dinov2_ksplit_workspace_bytes(const slime_vit_desc* d, int n_prefix, int n_crops, const slime_vit_ksplit* ks) {
+    return ks && n_prefix >= 1 && n_prefix <= 17 ? vit_workspace(d, n_crops, ks, dinov2_form(n_prefix)) : 0;
+}
+
+extern "C" int slime_dinov2_forward(const slime_vit_desc* d, int n_prefix, const void* pixels, int pix_dtype, int n, void* out, int out_dtype,
+                                    int keep_prefix, float* hidden_f32, float* states_f32, const slime_vit_ksplit* ks, void* ws,
+                                    size_t ws_bytes, void* stream) {
+    TRY(dinov2_prefix_ok(n_prefix));
+    return vit_run(d, pixels, pix_dtype, n, out, out_dtype, keep_prefix, hidden_f32, ws, ws_bytes, stream, nullptr, states_f32, ks,
+                   dinov2_form(n_prefix));
 }
 
 // ------------------------------------------------------------------------------------------------

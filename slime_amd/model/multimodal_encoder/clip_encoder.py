@@ -12,6 +12,7 @@ Differences that are deliberate and documented in DESIGN.md:
 """
 from __future__ import annotations
 
+import dataclasses
 import json
 import os
 from types import SimpleNamespace
@@ -75,10 +76,11 @@ class _VisionTransformer(nn.Module):
 class HipVisionModelBase(nn.Module):
     """What the HIP tower models share (CLIP layout: HipCLIPVisionModel; SigLIP layout: siglip_encoder.HipSiglipVisionModel): the
     parameter container's key handling, the packed-weight cache with one workspace per stream slot, the two-stream split of
-    ``encode`` and the ``k_split`` setting.  A subclass builds ``self.vision_model`` (the torch sub-modules are never called: they
-    only give the parameters their names) and says how its tower is packed and run."""
+    ``encode`` and the ``k_split`` setting, the HF-like ``forward``.  A subclass builds ``self.vision_model`` (the torch sub-modules
+    are never called: they only give the parameters their names) and says how its tower is packed (``ops.tower_forward`` runs all)."""
     TOP_LEVEL = ()            # first key components under ``vision_model.`` (a prefix-free 5.x key is recognised by them)
     DROPPED = ()              # key prefixes under ``vision_model.`` a checkpoint may carry and the tower never runs
+    STATES_K_SPLIT = True     # forward(output_hidden_states=True) runs its pass with ``k_split``, as encode() does
 
     def __init__(self, config, compute_dtype: torch.dtype = torch.bfloat16):
         super().__init__()
@@ -101,18 +103,18 @@ class HipVisionModelBase(nn.Module):
         """A parameter every tower of the layout has: its dtype / device are the model's."""
         raise NotImplementedError
 
-    def _pack(self, select_layer: int):
+    def _pack(self, select_layer: int) -> ops.PackedTower:
         raise NotImplementedError
 
-    def _share(self, base):
-        """A second packed object over ``base``'s weights with a workspace of its own (the second stream's slot)."""
-        raise NotImplementedError
+    def _share(self, base: ops.PackedTower) -> ops.PackedTower:
+        """A second packed object over ``base``'s weights with a workspace of its own (the second stream's slot) and no probe."""
+        return dataclasses.replace(base, ws=ops.Workspace(), probe=None)
 
     def _run(self, pt, pixel_values, out_dtype, keep_cls: bool, **kw):
-        raise NotImplementedError
+        return ops.tower_forward(pt, pixel_values, out_dtype, keep_cls, **kw)
 
     def _rows(self, keep_cls: bool) -> int:
-        raise NotImplementedError
+        return self.config.seq_len if keep_cls else self.config.num_patches
 
     # -- state dict: accept both HF key generations -------------------------------------------
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
@@ -189,12 +191,29 @@ class HipVisionModelBase(nn.Module):
         cur.wait_stream(side)
         return out
 
+    @torch.no_grad()
+    def forward(self, pixel_values: torch.Tensor, output_hidden_states: bool = False, **_):
+        """HF-like call: returns an object with ``hidden_states`` (L + 1 entries of all ``seq_len`` rows: the embeddings -- after
+        pre_layrnorm where the tower has one -- then the output of every layer: ONE tower pass over all L layers that snapshots the
+        fp32 residual stream after each; use :meth:`encode` on the hot path, which runs only the layers its state needs) and
+        ``last_hidden_state`` (HF: hidden_states[-1], without the final LayerNorm, which never runs here)."""
+        L = self.config.num_hidden_layers
+        if output_hidden_states:
+            ks = tuple(self.k_split) if self.STATES_K_SPLIT and self.k_split is not None else None
+            st = ops.tower_hidden_states(self.packed(L), pixel_values, k_split=ks).to(pixel_values.dtype)
+            hs = tuple(st[i] for i in range(L + 1))
+            return SimpleNamespace(hidden_states=hs, last_hidden_state=hs[-1])
+        return SimpleNamespace(hidden_states=None, last_hidden_state=self.encode(pixel_values, L, keep_cls=True))
+
 
 class HipCLIPVisionModel(HipVisionModelBase):
     """Parameter container with HF ``CLIPVisionModel`` state-dict keys (transformers-4.37 names,
     ``vision_model.`` prefix; prefix-free 5.x keys are accepted on load) whose forward is the HIP
     tower."""
     TOP_LEVEL = ("embeddings", "pre_layrnorm", "encoder", "post_layernorm")
+    # the CLIP states pass predates k_split (slime_vit_forward_states took none) and has always run unsplit, so with k_split set its
+    # hidden_states[i] are not encode()'s bits; the SigLIP and DINOv2 models pass k_split on.  Kept as it is: results do not move here
+    STATES_K_SPLIT = False
 
     def __init__(self, config: VisionConfig, compute_dtype: torch.dtype = torch.bfloat16):
         super().__init__(config, compute_dtype)
@@ -207,28 +226,6 @@ class HipCLIPVisionModel(HipVisionModelBase):
     def _pack(self, select_layer: int) -> ops.PackedTower:
         return ops.pack_tower(self.state_dict(), self.config, self.operand_dtype(), self.device, select_layer)
 
-    def _share(self, base: ops.PackedTower) -> ops.PackedTower:
-        return ops.PackedTower(base.cfg, base.dtype, base.layers_run, base.tensors, base.desc, act=base.act)
-
-    def _run(self, pt, pixel_values, out_dtype, keep_cls, **kw):
-        return ops.tower_forward(pt, pixel_values, out_dtype, keep_cls, **kw)
-
-    def _rows(self, keep_cls: bool) -> int:
-        return self.config.num_patches + (1 if keep_cls else 0)
-
-    @torch.no_grad()
-    def forward(self, pixel_values: torch.Tensor, output_hidden_states: bool = False, **_):
-        """HF-like call: returns an object with ``hidden_states`` (L+1 entries: embeddings after pre_layrnorm, then the output
-        of every layer -- ONE tower pass over all L layers that snapshots the fp32 residual stream after each,
-        ``slime_vit_forward_states``; use :meth:`encode` on the hot path, which runs only the layers its state needs) and
-        ``last_hidden_state`` (HF: hidden_states[-1], without post_layernorm)."""
-        L = self.config.num_hidden_layers
-        if output_hidden_states:
-            st = ops.tower_hidden_states(self.packed(L), pixel_values).to(pixel_values.dtype)
-            hs = tuple(st[i] for i in range(L + 1))
-            return SimpleNamespace(hidden_states=hs, last_hidden_state=hs[-1])
-        return SimpleNamespace(hidden_states=None, last_hidden_state=self.encode(pixel_values, L, keep_cls=True))
-
 
 def _read_hf_vision_config(path: str) -> VisionConfig:
     cfg = json.load(open(os.path.join(path, "config.json")))
@@ -240,14 +237,20 @@ def _read_hf_vision_config(path: str) -> VisionConfig:
                         hidden_act=cfg.get("hidden_act", "quick_gelu"))
 
 
-def _read_hf_weights(path: str) -> Dict[str, torch.Tensor]:
+def _clip_tower_key(k: str) -> bool:
+    """False for what a whole CLIPModel checkpoint holds beside its vision tower (text tower, projection heads, logit scale)."""
+    return "text_model" not in k and "projection" not in k and "logit_scale" not in k
+
+
+def _read_hf_weights(path: str, keep=_clip_tower_key) -> Dict[str, torch.Tensor]:
+    """The tensors of the directory's checkpoint whose key ``keep`` accepts (None: all of them -- ``projection`` is DINOv2's conv)."""
     st = os.path.join(path, "model.safetensors")
     if os.path.isfile(st):
         from safetensors.torch import load_file
         sd = load_file(st)
     else:
         sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu")
-    return {k: v for k, v in sd.items() if "text_model" not in k and "projection" not in k and "logit_scale" not in k}
+    return sd if keep is None else {k: v for k, v in sd.items() if keep(k)}
 
 
 def _resolve_local(name: str) -> str:
@@ -262,18 +265,24 @@ def _resolve_local(name: str) -> str:
             f"Pass a directory with config.json + model.safetensors, or '{SYNTHETIC_PREFIX}<seed>'.") from e
 
 
-def check_tower_keys(result, source: str) -> None:
-    """The parameter container starts uninitialised, so a checkpoint with another naming scheme (open_clip, a partial
-    file) must not load silently: only the dead ``post_layernorm`` (never run: hidden_states[-2]) and HF's ``position_ids``
-    buffer may be absent, and nothing may be left over."""
-    missing = [k for k in result.missing_keys if "post_layernorm" not in k and "position_ids" not in k]
-    unexpected = [k for k in result.unexpected_keys if "position_ids" not in k]
+CLIP_TOLERATED = ("post_layernorm", "position_ids")
+
+
+def check_tower_keys(result, source: str, layout: str = "CLIP", tolerated=CLIP_TOLERATED) -> None:
+    """The parameter container starts uninitialised, so a checkpoint with another naming scheme (open_clip, a partial file,
+    another family's layout) must not load silently: only keys that contain one of ``tolerated`` may be absent -- what the tower
+    never runs: the dead ``post_layernorm`` (hidden_states[-2]) and HF's ``position_ids`` buffer for the CLIP and SigLIP layouts --
+    and nothing may be left over but, where it is tolerated, that buffer."""
+    missing = [k for k in result.missing_keys if not any(t in k for t in tolerated)]
+    unexpected = [k for k in result.unexpected_keys if not ("position_ids" in tolerated and "position_ids" in k)]
     if missing or unexpected:
-        raise RuntimeError(f"vision tower checkpoint {source!r} does not match the CLIP ViT layout: "
+        raise RuntimeError(f"vision tower checkpoint {source!r} does not match the {layout} ViT layout: "
                            f"{len(missing)} missing (e.g. {missing[:3]}), {len(unexpected)} unexpected (e.g. {unexpected[:3]})")
 
 
 class CLIPVisionTower(nn.Module):
+    LAYOUT, TOLERATED = "CLIP", CLIP_TOLERATED       # check_tower_keys' arguments
+
     def __init__(self, vision_tower, args, delay_load=False):
         super().__init__()
         self.is_loaded = False
@@ -293,22 +302,26 @@ class CLIPVisionTower(nn.Module):
             return VisionConfig()
         return _read_hf_vision_config(_resolve_local(self.vision_tower_name))
 
+    def _source(self):
+        """(model class, config, state dict, image processor) of the named tower, the config checked: a synthetic seed (the
+        offline stand-in for the hub checkpoint) or a directory."""
+        name = self.vision_tower_name
+        if name.startswith(SYNTHETIC_PREFIX):
+            cfg, proc = VisionConfig(), ClipImageProcessor()
+            sd = make_tower_state_dict(cfg, seed=int(name[len(SYNTHETIC_PREFIX):] or 1234))
+        else:
+            path = _resolve_local(name)
+            cfg, sd, proc = _read_hf_vision_config(path), _read_hf_weights(path), ClipImageProcessor.from_pretrained(path)
+        ops.tower_act(cfg)          # quick_gelu (OpenAI CLIP) or gelu (OpenCLIP); anything else (gelu_new, ...) is refused by name
+        return HipCLIPVisionModel, cfg, sd, proc
+
     def load_model(self, device_map=None):
         if self.is_loaded:
             print("{} is already loaded, `load_model` called again, skipping.".format(self.vision_tower_name))
             return
-        name = self.vision_tower_name
-        if name.startswith(SYNTHETIC_PREFIX):       # offline stand-in for the hub checkpoint
-            cfg = VisionConfig()
-            sd = make_tower_state_dict(cfg, seed=int(name[len(SYNTHETIC_PREFIX):] or 1234))
-            self.image_processor = ClipImageProcessor()
-        else:
-            path = _resolve_local(name)
-            cfg, sd = _read_hf_vision_config(path), _read_hf_weights(path)
-            self.image_processor = ClipImageProcessor.from_pretrained(path)
-        ops.tower_act(cfg)          # quick_gelu (OpenAI CLIP) or gelu (OpenCLIP); anything else (gelu_new, ...) is refused by name
-        self.vision_tower = HipCLIPVisionModel(cfg, self._compute_dtype)
-        check_tower_keys(self.vision_tower.load_state_dict(sd, strict=False), name)
+        model, cfg, sd, self.image_processor = self._source()
+        self.vision_tower = model(cfg, self._compute_dtype)
+        check_tower_keys(self.vision_tower.load_state_dict(sd, strict=False), self.vision_tower_name, self.LAYOUT, self.TOLERATED)
         if device_map not in (None, "auto") and not isinstance(device_map, dict):
             self.vision_tower.to(device_map)
         self.vision_tower.requires_grad_(False)

@@ -17,8 +17,6 @@ from __future__ import annotations
 
 import json
 import os
-from types import SimpleNamespace
-from typing import Dict
 
 import torch
 import torch.nn as nn
@@ -26,7 +24,7 @@ import torch.nn as nn
 from ... import ops
 from ...image_processor import Dinov2ImageProcessor
 from ...weights import Dinov2VisionConfig, DINOV2_L_REG4_224, make_dinov2_state_dict, strip_dinov2_prefix
-from .clip_encoder import CLIPVisionTower, HipVisionModelBase, _resolve_local
+from .clip_encoder import CLIPVisionTower, HipVisionModelBase, _read_hf_weights, _resolve_local
 
 SYNTHETIC_DINOV2_PREFIX = "synthetic-dinov2:"
 DINOV2_MODEL_TYPES = ("dinov2", "dinov2_with_registers")
@@ -124,29 +122,8 @@ class HipDinov2VisionModel(HipVisionModelBase):
     def _anchor(self) -> torch.Tensor:
         return self.vision_model.embeddings.cls_token
 
-    def _pack(self, select_layer: int) -> ops.PackedDinov2Tower:
+    def _pack(self, select_layer: int) -> ops.PackedTower:
         return ops.pack_dinov2_tower(self.state_dict(), self.config, self.operand_dtype(), self.device, select_layer)
-
-    def _share(self, base: ops.PackedDinov2Tower) -> ops.PackedDinov2Tower:
-        return ops.PackedDinov2Tower(base.cfg, base.dtype, base.layers_run, base.tensors, base.desc)
-
-    def _run(self, pt, pixel_values, out_dtype, keep_cls, **kw):
-        return ops.dinov2_tower_forward(pt, pixel_values, out_dtype, keep_prefix=keep_cls, **kw)
-
-    def _rows(self, keep_cls: bool) -> int:
-        return self.config.seq_len if keep_cls else self.config.num_patches
-
-    @torch.no_grad()
-    def forward(self, pixel_values: torch.Tensor, output_hidden_states: bool = False, **_):
-        """HF-like call: ``hidden_states`` (L + 1 entries of all S = n_prefix + P rows: the embeddings, then the output of every
-        layer) and ``last_hidden_state`` = hidden_states[-1], without the final layernorm (never run here)."""
-        L = self.config.num_hidden_layers
-        if output_hidden_states:
-            ks = None if self.k_split is None else tuple(self.k_split)
-            st = ops.dinov2_tower_hidden_states(self.packed(L), pixel_values, k_split=ks).to(pixel_values.dtype)
-            hs = tuple(st[i] for i in range(L + 1))
-            return SimpleNamespace(hidden_states=hs, last_hidden_state=hs[-1])
-        return SimpleNamespace(hidden_states=None, last_hidden_state=self.encode(pixel_values, L, keep_cls=True))
 
 
 def is_dinov2_dir(path: str) -> bool:
@@ -191,26 +168,11 @@ def _read_dinov2_config(path: str) -> Dinov2VisionConfig:
                               model_type=model_type, **v)
 
 
-def check_dinov2_keys(result, source: str) -> None:
-    """As ``check_tower_keys``: only the never-read ``mask_token`` and ``layernorm`` may be absent, nothing may be left over -- a CLIP
-    or SigLIP checkpoint does not load as DINOv2."""
-    missing = [k for k in result.missing_keys if not k.endswith("embeddings.mask_token") and ".layernorm." not in k]
-    unexpected = list(result.unexpected_keys)
-    if missing or unexpected:
-        raise RuntimeError(f"vision tower checkpoint {source!r} does not match the DINOv2 ViT layout: "
-                           f"{len(missing)} missing (e.g. {missing[:3]}), {len(unexpected)} unexpected (e.g. {unexpected[:3]})")
-
-
-def _dinov2_weights(path: str) -> Dict[str, torch.Tensor]:
-    """The checkpoint's tensors (``_read_hf_weights`` drops keys containing ``projection``: the CLIP heads -- here that is the conv)."""
-    st = os.path.join(path, "model.safetensors")
-    if os.path.isfile(st):
-        from safetensors.torch import load_file
-        return load_file(st)
-    return torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu")
-
-
 class Dinov2VisionTower(CLIPVisionTower):
+    # only the never-read ``mask_token`` and ``layernorm`` may be absent, nothing may be left over: a CLIP or SigLIP checkpoint does
+    # not load as DINOv2
+    LAYOUT, TOLERATED = "DINOv2", ("embeddings.mask_token", ".layernorm.")
+
     def __init__(self, vision_tower, args, delay_load=False):
         feature = getattr(args, "mm_vision_select_feature", "patch")
         if feature not in ("patch", "cls_patch"):
@@ -228,24 +190,16 @@ class Dinov2VisionTower(CLIPVisionTower):
     def _config_only(self) -> Dinov2VisionConfig:
         return self._cfg
 
-    def load_model(self, device_map=None):
-        if self.is_loaded:
-            print("{} is already loaded, `load_model` called again, skipping.".format(self.vision_tower_name))
-            return
-        name, cfg = self.vision_tower_name, self._cfg
+    def _source(self):
+        cfg = self._cfg                              # read and checked at construction
         if self._seed is not None:                   # offline stand-in: ViT-L/14, 4 registers, table for 37 x 37, run at 224
             sd = make_dinov2_state_dict(cfg, seed=self._seed)
-            self.image_processor = Dinov2ImageProcessor(cfg.image_size * 256 // 224, cfg.image_size)
+            proc = Dinov2ImageProcessor(cfg.image_size * 256 // 224, cfg.image_size)
         else:
-            path = _resolve_local(name)
-            sd = _dinov2_weights(path)
-            self.image_processor = Dinov2ImageProcessor.from_pretrained(path, cfg.image_size)
-        self.vision_tower = HipDinov2VisionModel(cfg, self._compute_dtype)
-        check_dinov2_keys(self.vision_tower.load_state_dict(sd, strict=False), name)
-        if device_map not in (None, "auto") and not isinstance(device_map, dict):
-            self.vision_tower.to(device_map)
-        self.vision_tower.requires_grad_(False)
-        self.is_loaded = True
+            path = _resolve_local(self.vision_tower_name)
+            sd = _read_hf_weights(path, keep=None)   # every key: ``projection`` is the conv here
+            proc = Dinov2ImageProcessor.from_pretrained(path, cfg.image_size)
+        return HipDinov2VisionModel, cfg, sd, proc
 
     def _select(self, image_features):
         """``feature_select`` on an HF-like output (all S rows per state)."""

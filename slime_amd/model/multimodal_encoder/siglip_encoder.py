@@ -12,7 +12,6 @@ from __future__ import annotations
 
 import json
 import os
-from types import SimpleNamespace
 from typing import Dict
 
 import torch
@@ -55,29 +54,8 @@ class HipSiglipVisionModel(HipVisionModelBase):
     def _anchor(self) -> torch.Tensor:
         return self.vision_model.embeddings.position_embedding.weight
 
-    def _pack(self, select_layer: int) -> ops.PackedSiglipTower:
+    def _pack(self, select_layer: int) -> ops.PackedTower:
         return ops.pack_siglip_tower(self.state_dict(), self.config, self.operand_dtype(), self.device, select_layer)
-
-    def _share(self, base: ops.PackedSiglipTower) -> ops.PackedSiglipTower:
-        return ops.PackedSiglipTower(base.cfg, base.dtype, base.layers_run, base.tensors, base.desc)
-
-    def _run(self, pt, pixel_values, out_dtype, keep_cls, **kw):
-        return ops.siglip_tower_forward(pt, pixel_values, out_dtype, **kw)        # no class token: every call returns all P rows
-
-    def _rows(self, keep_cls: bool) -> int:
-        return self.config.num_patches
-
-    @torch.no_grad()
-    def forward(self, pixel_values: torch.Tensor, output_hidden_states: bool = False, **_):
-        """HF-like call: ``hidden_states`` (L + 1 entries: the embeddings, then the output of every layer) and
-        ``last_hidden_state`` = hidden_states[-1], without post_layernorm (never run here)."""
-        L = self.config.num_hidden_layers
-        if output_hidden_states:
-            ks = None if self.k_split is None else tuple(self.k_split)
-            st = ops.siglip_tower_hidden_states(self.packed(L), pixel_values, k_split=ks).to(pixel_values.dtype)
-            hs = tuple(st[i] for i in range(L + 1))
-            return SimpleNamespace(hidden_states=hs, last_hidden_state=hs[-1])
-        return SimpleNamespace(hidden_states=None, last_hidden_state=self.encode(pixel_values, L))
 
 
 def read_hf_config(path: str) -> dict:
@@ -108,17 +86,11 @@ def _tower_keys_only(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return {k: v for k, v in sd.items() if not k.startswith("text_model") and k not in ("logit_scale", "logit_bias")}
 
 
-def check_siglip_keys(result, source: str) -> None:
-    """As ``check_tower_keys``: only the never-run ``post_layernorm`` may be absent (``head.*`` is dropped on load), nothing may be
-    left over -- a CLIP-layout checkpoint (class_embedding, pre_layrnorm) does not load as SigLIP."""
-    missing = [k for k in result.missing_keys if "post_layernorm" not in k and "position_ids" not in k]
-    unexpected = [k for k in result.unexpected_keys if "position_ids" not in k]
-    if missing or unexpected:
-        raise RuntimeError(f"vision tower checkpoint {source!r} does not match the SigLIP ViT layout: "
-                           f"{len(missing)} missing (e.g. {missing[:3]}), {len(unexpected)} unexpected (e.g. {unexpected[:3]})")
-
-
 class SigLipVisionTower(CLIPVisionTower):
+    # only the never-run ``post_layernorm`` may be absent (``head.*`` is dropped on load), nothing may be left over: a CLIP-layout
+    # checkpoint (class_embedding, pre_layrnorm) does not load as SigLIP
+    LAYOUT = "SigLIP"
+
     def __init__(self, vision_tower, args, delay_load=False):
         feature = getattr(args, "mm_vision_select_feature", "patch")
         if feature != "patch":
@@ -135,26 +107,17 @@ class SigLipVisionTower(CLIPVisionTower):
             return SiglipVisionConfig()
         return _read_siglip_config(_resolve_local(self.vision_tower_name))
 
-    def load_model(self, device_map=None):
-        if self.is_loaded:
-            print("{} is already loaded, `load_model` called again, skipping.".format(self.vision_tower_name))
-            return
-        name, seed = self.vision_tower_name, self._synthetic_seed()
+    def _source(self):
+        seed = self._synthetic_seed()
         if seed is not None:                         # offline stand-in for siglip-large-patch16-384
             cfg = SiglipVisionConfig()
-            sd = make_siglip_state_dict(cfg, seed=seed)
-            self.image_processor = SiglipImageProcessor(cfg.image_size)
+            sd, proc = make_siglip_state_dict(cfg, seed=seed), SiglipImageProcessor(cfg.image_size)
         else:
-            path = _resolve_local(name)
+            path = _resolve_local(self.vision_tower_name)
             cfg, sd = _read_siglip_config(path), _tower_keys_only(_read_hf_weights(path))
-            self.image_processor = SiglipImageProcessor.from_pretrained(path, cfg.image_size)
+            proc = SiglipImageProcessor.from_pretrained(path, cfg.image_size)
         ops.check_siglip_config(cfg)                 # activation, head_dim, patches per side, intermediate size: refused by name
-        self.vision_tower = HipSiglipVisionModel(cfg, self._compute_dtype)
-        check_siglip_keys(self.vision_tower.load_state_dict(sd, strict=False), name)
-        if device_map not in (None, "auto") and not isinstance(device_map, dict):
-            self.vision_tower.to(device_map)
-        self.vision_tower.requires_grad_(False)
-        self.is_loaded = True
+        return HipSiglipVisionModel, cfg, sd, proc
 
     def _select(self, image_features):
         return image_features                        # 'patch' = all P tokens

@@ -14,7 +14,6 @@ import os
 import threading
 import weakref
 from dataclasses import dataclass, field
-from types import SimpleNamespace
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
@@ -291,18 +290,20 @@ def attention(q, k, v, heads: int, head_dim: int) -> torch.Tensor:
 
 @dataclass
 class PackedTower:
-    cfg: VisionConfig
+    """A packed CLIP, SigLIP or DINOv2 tower (``pack_tower`` / ``pack_siglip_tower`` / ``pack_dinov2_tower``)."""
+    cfg: VisionConfig                    # or SiglipVisionConfig / Dinov2VisionConfig, by ``form``
     dtype: torch.dtype
     layers_run: int
     tensors: Dict[str, torch.Tensor]
     desc: _lib.VitDesc
     ws: Workspace = field(default_factory=Workspace)
-    probe: Optional[tuple] = None        # (layer, kernel id, start event, stop event): in-situ kernel timing
-    act: int = _lib.ACT_QUICKGELU        # SLIME_ACT_* of cfg.hidden_act: anything but quick-GELU runs through slime_vit_forward_opts
+    probe: Optional[tuple] = None        # (layer, kernel id, start event, stop event): in-situ kernel timing (CLIP form)
+    act: int = _lib.ACT_QUICKGELU        # SLIME_ACT_* of cfg.hidden_act (CLIP form: what slime_vit_forward_opts is given)
+    form: str = "clip"                   # "clip" | "siglip" | "dinov2": the C entry that runs the tower (``_tower_call``)
 
     @property
     def device(self):
-        return self.tensors["cls"].device
+        return self.tensors["pos"].device
 
 
 def tower_act(cfg: VisionConfig) -> int:
@@ -344,8 +345,7 @@ def tower_host_tensors(state_dict: Dict[str, torch.Tensor], cfg: VisionConfig, d
     [D, kpad] matrix, and per layer (stacked along dim 0, ``layers_for_select`` layers) [q; k; v] with LayerNorm1 and the q scale
     dh^-0.5 log2(e) folded in (``fold_ln``), fc1 with LayerNorm2 folded in, out_proj and fc2 as they are.  Matrices in ``dtype``,
     everything else fp32; ``dtype=None``: nothing is rounded, every tensor float64."""
-    if dtype not in (None, torch.bfloat16, torch.float16):
-        raise ValueError("tower compute dtype must be bf16 or fp16 (MFMA operand type); fp32 I/O is supported")
+    _check_operand_dtype(dtype, allow_none=True)
     sd = strip_tower_prefix(state_dict)
     L = layers_for_select(cfg, select_layer)
     f32, tt = _host_casts(dtype)
@@ -371,73 +371,101 @@ def _host_casts(dtype: Optional[torch.dtype]):
     return f32, tt
 
 
-def _conv_matrix(sd, cfg, tt) -> torch.Tensor:
+def _conv_matrix(sd, cfg, tt, key: str = "embeddings.patch_embedding.weight") -> torch.Tensor:
     """The patch-embed conv weight as a [D, kpad] matrix (column order Conv2d.weight.flatten(1), zero padded to a multiple of 64)."""
     D, P2 = cfg.hidden_size, 3 * cfg.patch_size * cfg.patch_size
     pw = torch.zeros((D, (P2 + 63) // 64 * 64), dtype=torch.float32)
-    pw[:, :P2] = sd["embeddings.patch_embedding.weight"].detach().float().cpu().reshape(D, P2)
+    pw[:, :P2] = sd[key].detach().float().cpu().reshape(D, P2)
     return tt(pw)
 
 
-def _layer_host_tensors(T: Dict[str, torch.Tensor], sd, cfg, dtype: Optional[torch.dtype], L: int) -> None:
-    """The per-layer part of ``tower_host_tensors`` (the CLIP and SigLIP layouts share the layer keys): adds the stacked, folded
-    tensors of the first ``L`` layers to ``T``."""
+class LayerKeys(NamedTuple):
+    """A checkpoint layout's names under one encoder layer (``layer.format(i)`` + name + ".weight" / ".bias"); ``scale_o`` /
+    ``scale_fc2``: the vectors that scale the outputs of out_proj / fc2 (DINOv2's LayerScale), or None."""
+    layer: str
+    q: str
+    k: str
+    v: str
+    o: str
+    ln1: str
+    ln2: str
+    fc1: str = "mlp.fc1"
+    fc2: str = "mlp.fc2"
+    scale_o: Optional[str] = None
+    scale_fc2: Optional[str] = None
+
+
+CLIP_LAYER_KEYS = LayerKeys("encoder.layers.{}.", "self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.out_proj",
+                            "layer_norm1", "layer_norm2")        # the SigLIP layout's as well
+DINOV2_LAYER_KEYS = LayerKeys("encoder.layer.{}.", "attention.attention.query", "attention.attention.key", "attention.attention.value",
+                              "attention.output.dense", "norm1", "norm2", scale_o="layer_scale1.lambda1", scale_fc2="layer_scale2.lambda1")
+
+
+def _layer_host_tensors(T: Dict[str, torch.Tensor], sd, cfg, dtype: Optional[torch.dtype], L: int,
+                        keys: LayerKeys = CLIP_LAYER_KEYS) -> None:
+    """The per-layer part of the ``*_host_tensors`` functions: adds the stacked, folded tensors of the first ``L`` layers to ``T``."""
     D = cfg.hidden_size
-    scale = cfg.head_dim ** -0.5 * LOG2E                     # logits in log2 units (slime_attention contract)
     f32, tt = _host_casts(dtype)
+    if L == 0:
+        return
+    rs = torch.ones(3 * D, dtype=torch.float64)
+    rs[:D] = cfg.head_dim ** -0.5 * LOG2E                      # q rows carry dh^-0.5 * log2 e: logits in log2 units (slime_attention contract)
+    cols = {k: [] for k in ("w_qkv", "b_qkv", "colsum_qkv", "w_fc1", "b_fc1", "colsum_fc1", "w_o", "b_o", "w_fc2", "b_fc2")}
+    for i in range(L):
+        p = keys.layer.format(i)
+        Wm = torch.cat([sd[p + n + ".weight"].float() for n in (keys.q, keys.k, keys.v)], 0)
+        bm = torch.cat([sd[p + n + ".bias"].float() for n in (keys.q, keys.k, keys.v)], 0)
+        for k, v in zip(("w_qkv", "b_qkv", "colsum_qkv"), fold_ln(Wm, bm, sd[p + keys.ln1 + ".weight"], sd[p + keys.ln1 + ".bias"], rs, dtype)):
+            cols[k].append(v)
+        for k, v in zip(("w_fc1", "b_fc1", "colsum_fc1"), fold_ln(sd[p + keys.fc1 + ".weight"], sd[p + keys.fc1 + ".bias"],
+                                                                  sd[p + keys.ln2 + ".weight"], sd[p + keys.ln2 + ".bias"], None, dtype)):
+            cols[k].append(v)
+        for w, b, lin, lam in (("w_o", "b_o", keys.o, keys.scale_o), ("w_fc2", "b_fc2", keys.fc2, keys.scale_fc2)):
+            Wm, bm = sd[p + lin + ".weight"], sd[p + lin + ".bias"]
+            if lam is not None:                                # output feature j of the Linear is scaled by lambda[j]: row j of W, b[j]
+                s = sd[p + lam].detach().double().cpu()
+                Wm, bm = Wm.detach().double().cpu() * s[:, None], bm.detach().double().cpu() * s
+            cols[w].append(tt(Wm))
+            cols[b].append(f32(bm))
+    for k, v in cols.items():
+        T[k] = torch.stack(v).contiguous()
+
+
+def _check_operand_dtype(dtype: Optional[torch.dtype], allow_none: bool = False) -> None:
+    if dtype not in (torch.bfloat16, torch.float16) and not (allow_none and dtype is None):
+        raise ValueError("tower compute dtype must be bf16 or fp16 (MFMA operand type); fp32 I/O is supported")
+
+
+def _pack_tail(who: str, form: str, host: Dict[str, torch.Tensor], cfg, dtype: torch.dtype, device, L: int, check, act=_lib.ACT_QUICKGELU):
+    """What the three ``pack_*`` share behind their config checks: the host tensors ``host`` on ``device``, the four layer matrices
+    and the conv weight in MFMA-fragment order, the descriptor, and the driver's own validation (``check(lib, desc)``, the form's
+    slime_*_check) at PACK time: a geometry the fused front end cannot run (more than 24 patches per side, image not a multiple of
+    8, ...) is refused here with the limit named, not by the first forward."""
+    T: Dict[str, torch.Tensor] = {k: v.to(device).contiguous() for k, v in host.items()}
     if L > 0:
-        p = "encoder.layers.{}."
-
-        def stack(fmt, conv):
-            return torch.stack([conv(sd[fmt.format(i)]) for i in range(L)]).contiguous()
-
-        rs = torch.ones(3 * D, dtype=torch.float64)
-        rs[:D] = scale                                         # q rows carry dh^-0.5 * log2 e (slime_attention contract)
-        wq, bq, cq, w1, b1, c1 = [], [], [], [], [], []
-        for i in range(L):
-            q = f"encoder.layers.{i}."
-            a = q + "self_attn."
-            Wm = torch.cat([sd[a + "q_proj.weight"].float(), sd[a + "k_proj.weight"].float(), sd[a + "v_proj.weight"].float()], 0)
-            bm = torch.cat([sd[a + "q_proj.bias"].float(), sd[a + "k_proj.bias"].float(), sd[a + "v_proj.bias"].float()], 0)
-            Wt, bp, cs = fold_ln(Wm, bm, sd[q + "layer_norm1.weight"], sd[q + "layer_norm1.bias"], rs, dtype)
-            wq.append(Wt); bq.append(bp); cq.append(cs)
-            Wt, bp, cs = fold_ln(sd[q + "mlp.fc1.weight"], sd[q + "mlp.fc1.bias"], sd[q + "layer_norm2.weight"], sd[q + "layer_norm2.bias"],
-                                 None, dtype)
-            w1.append(Wt); b1.append(bp); c1.append(cs)
-
-        def host_stack(ts):
-            return torch.stack(ts).contiguous()
-
-        T["w_qkv"], T["b_qkv"], T["colsum_qkv"] = host_stack(wq), host_stack(bq), host_stack(cq)
-        T["w_fc1"], T["b_fc1"], T["colsum_fc1"] = host_stack(w1), host_stack(b1), host_stack(c1)
-        T["w_o"], T["b_o"] = stack(p + "self_attn.out_proj.weight", tt), stack(p + "self_attn.out_proj.bias", f32)
-        T["w_fc2"], T["b_fc2"] = stack(p + "mlp.fc2.weight", tt), stack(p + "mlp.fc2.bias", f32)
+        # fragment-order images (the direct-B kernel loads them straight into registers, the LDS-staged kernels DMA from them);
+        # the row-major tensors are dropped unless SLIME_KEEP_ROW_MAJOR=1
+        pack_static(T, ("w_qkv", "w_o", "w_fc1", "w_fc2"))
+    T["patch_w_frag"] = pack_b_frag(T["patch_w"])          # the front end (slime_patch_embed_*) reads this image only
+    if T["patch_w_frag"] is None:
+        if not T["patch_w"].is_cuda:
+            raise _lib.SlimeHipError(f"{who}: weights are packed on the GPU (slime_gemm_pack_b): slime_amd has no CPU path")
+        raise ValueError(f"{who}: the patch-embed weight could not be packed (hidden size and padded patch size must be multiples of 64)")
+    T["patch_w"] = None
+    d = _vit_desc(T, cfg, dtype, L)
+    _lib.check(check(_lib.load(), C.byref(d)), who)
+    return PackedTower(cfg, dtype, L, T, d, act=act, form=form)
 
 
 def pack_tower(state_dict: Dict[str, torch.Tensor], cfg: VisionConfig, dtype: torch.dtype, device,
                select_layer: int = -2) -> PackedTower:
     """HF CLIPVisionModel state dict (either key generation) -> device tensors in the kernels' layout (``tower_host_tensors`` on
     ``device``, the four layer matrices and the conv weight also in MFMA-fragment order)."""
-    if dtype not in (torch.bfloat16, torch.float16):
-        raise ValueError("tower compute dtype must be bf16 or fp16 (MFMA operand type); fp32 I/O is supported")
+    _check_operand_dtype(dtype)
     act = tower_act(cfg)
     L = layers_for_select(cfg, select_layer)
-    T: Dict[str, torch.Tensor] = {k: v.to(device).contiguous() for k, v in tower_host_tensors(state_dict, cfg, dtype, select_layer).items()}
-    if L > 0:
-        # fragment-order images (the direct-B kernel loads them straight into registers, the LDS-staged kernels DMA from them);
-        # the row-major tensors are dropped unless SLIME_KEEP_ROW_MAJOR=1
-        pack_static(T, ("w_qkv", "w_o", "w_fc1", "w_fc2"))
-    T["patch_w_frag"] = pack_b_frag(T["patch_w"])          # the front end (slime_patch_embed_prenorm) reads this image only
-    if T["patch_w_frag"] is None:
-        if not T["patch_w"].is_cuda:
-            raise _lib.SlimeHipError("pack_tower: weights are packed on the GPU (slime_gemm_pack_b): slime_amd has no CPU path")
-        raise ValueError("pack_tower: the patch-embed weight could not be packed (hidden size and padded patch size must be multiples of 64)")
-    T["patch_w"] = None
-    d = _vit_desc(T, cfg, dtype, L)
-    # the driver's own validation, at PACK time: a geometry the fused front end cannot run (more than 24 patches per side, image
-    # not a multiple of 8, ...) is refused here with the limit named, not by the first forward (ADVICE r5)
-    _lib.check(_lib.load().slime_vit_check(C.byref(d)), "pack_tower")
-    return PackedTower(cfg, dtype, L, T, d, act=act)
+    return _pack_tail("pack_tower", "clip", tower_host_tensors(state_dict, cfg, dtype, select_layer), cfg, dtype, device, L,
+                      lambda lib, d: lib.slime_vit_check(d), act)
 
 
 def _vit_desc(T: Dict[str, Optional[torch.Tensor]], cfg, dtype: torch.dtype, L: int) -> "_lib.VitDesc":
@@ -452,25 +480,68 @@ def _vit_desc(T: Dict[str, Optional[torch.Tensor]], cfg, dtype: torch.dtype, L: 
     return d
 
 
+def _tower_pixels(pt: PackedTower, pixels: torch.Tensor) -> torch.Tensor:
+    """pixels as the C entries take them: [N, 3, S, S] of the size the tower was packed for, fp32 or the operand dtype, contiguous."""
+    _require_cuda(pixels, "pixels")
+    s = pt.cfg.image_size
+    if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != s or pixels.shape[3] != s:
+        # HF raises on a size mismatch too (modeling_clip.py:204-207)
+        raise ValueError(f"Input image size ({tuple(pixels.shape[2:])}) doesn't match model ({s}*{s}).")
+    if pixels.dtype not in (torch.float32, pt.dtype):
+        pixels = pixels.to(pt.dtype)
+    return pixels.contiguous()
+
+
+def _tower_call(pt: PackedTower, pixels, out, keep: bool, hidden, states, k_split) -> None:
+    """One tower pass through the form's C entry (any of out / hidden / states; ``keep``: ``out`` has the rows in front of the patches
+    too): slime_vit_forward_opts with the tower's activation, slime_siglip_forward or slime_dinov2_forward.  A CLIP tower with a
+    timing probe set makes its out / hidden pass through slime_vit_forward_ex, the one entry that takes a probe."""
+    lib = _lib.load()
+    n, ks, d = pixels.shape[0], None, C.byref(pt.desc)
+    if k_split is not None:
+        if len(k_split) != 4:
+            raise ValueError("tower_forward: k_split is (qkv, out_proj, fc1, fc2)")
+        ks = _lib.VitKsplit(*(int(v) for v in k_split))
+    probed = pt.form == "clip" and pt.probe is not None and states is None
+    if probed and ks is not None:
+        raise ValueError("tower_forward: the timing probe goes with k_split=None (slime_vit_forward_ex)")
+    if probed and pt.act != _lib.ACT_QUICKGELU:
+        raise ValueError("tower_forward: the timing probe (slime_vit_forward_ex) is built for quick-GELU towers")
+    ksp = C.byref(ks) if ks is not None else None
+    desc = (d, pt.cfg.n_prefix) if pt.form == "dinov2" else (d,)             # the DINOv2 entries take n_prefix behind the descriptor
+    family = {"clip": "vit", "siglip": "siglip", "dinov2": "dinov2"}[pt.form]
+    if ks is not None:
+        need = getattr(lib, f"slime_{family}_ksplit_workspace_bytes")(*desc, n, ksp)
+    else:
+        need = getattr(lib, f"slime_{family}_workspace_bytes")(*desc, n)
+    base, avail = pt.ws.aligned(need, pixels.device)
+    px = (pixels.data_ptr(), dtype_code(pixels.dtype), n, _ptr(out), dtype_code(out.dtype) if out is not None else _lib.F32)
+    if probed:
+        layer, kernel, e0, e1 = pt.probe
+        probe = C.byref(_lib.Probe(int(layer), int(kernel), e0.cuda_event, e1.cuda_event))
+        _lib.check(lib.slime_vit_forward_ex(d, *px, int(keep), _ptr(hidden), base, avail, _stream(), probe), "slime_vit_forward")
+    elif pt.form == "clip":
+        _lib.check(lib.slime_vit_forward_opts(d, C.byref(_lib.VitOpts(pt.act)), *px, int(keep), _ptr(hidden), _ptr(states), ksp, base, avail,
+                                              _stream()), "slime_vit_forward_opts")
+    elif pt.form == "siglip":                                 # no rows in front of the patches: no keep flag
+        _lib.check(lib.slime_siglip_forward(d, *px, _ptr(hidden), _ptr(states), ksp, base, avail, _stream()), "slime_siglip_forward")
+    else:
+        _lib.check(lib.slime_dinov2_forward(*desc, *px, int(keep), _ptr(hidden), _ptr(states), ksp, base, avail, _stream()),
+                   "slime_dinov2_forward")
+
+
 def tower_forward(pt: PackedTower, pixels: torch.Tensor, out_dtype: Optional[torch.dtype] = None,
                   keep_cls: bool = False, want_hidden: bool = False, out: Optional[torch.Tensor] = None,
                   k_split: Optional[Sequence[int]] = None):
-    """pixels [N,3,S,S] (fp32 or the tower dtype) -> features [N, P(+1), D] in out_dtype (written into ``out`` if given:
-    a contiguous [N, P(+1), D] tensor or leading-dim slice of one).
-    k_split = (qkv, out_proj, fc1, fc2): run those layer GEMMs as deterministic split-K pairs (slime_vit_forward_ksplit; 1 =
-    unsplit).  None (the default) is slime_vit_forward_ex exactly.  For one setting the result does not depend on how the crops are
-    cut into calls; it is not bit-identical to another setting's.
-    A tower whose activation is not quick-GELU (``pt.act``) makes the same passes through slime_vit_forward_opts."""
-    lib = _lib.load()
-    _require_cuda(pixels, "pixels")
-    cfg = pt.cfg
-    if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != cfg.image_size or pixels.shape[3] != cfg.image_size:
-        # HF raises on a size mismatch too (modeling_clip.py:204-207)
-        raise ValueError(f"Input image size ({tuple(pixels.shape[2:])}) doesn't match model ({cfg.image_size}*{cfg.image_size}).")
-    if pixels.dtype not in (torch.float32, pt.dtype):
-        pixels = pixels.to(pt.dtype)
-    pixels = pixels.contiguous()
-    n = pixels.shape[0]
+    """pixels [N,3,S,S] (fp32 or the tower dtype) -> hidden_states[select_layer] in out_dtype (written into ``out`` if given: a
+    contiguous tensor of that shape or leading-dim slice of one): the P patch rows [N, P, D], or with ``keep_cls`` all
+    ``cfg.seq_len`` rows -- the class token in front for a CLIP tower, the class token and the registers for a DINOv2 tower, nothing
+    more for a SigLIP tower.  ``want_hidden`` adds the fp32 state with all rows.
+    k_split = (qkv, out_proj, fc1, fc2): run those layer GEMMs as deterministic split-K pairs (1 = unsplit).  None (the default) is
+    the unsplit pass.  For one setting the result does not depend on how the crops are cut into calls; it is not bit-identical to
+    another setting's."""
+    pixels = _tower_pixels(pt, pixels)
+    cfg, n = pt.cfg, pixels.shape[0]
     out_dtype = out_dtype or pixels.dtype
     rows = cfg.seq_len if keep_cls else cfg.num_patches
     if out is None:
@@ -478,66 +549,32 @@ def tower_forward(pt: PackedTower, pixels: torch.Tensor, out_dtype: Optional[tor
     elif tuple(out.shape) != (n, rows, cfg.hidden_size) or out.dtype != out_dtype or not out.is_contiguous():
         raise ValueError("tower_forward: out must be a contiguous [N, rows, hidden] tensor of the output dtype")
     hidden = torch.empty((n, cfg.seq_len, cfg.hidden_size), dtype=torch.float32, device=pixels.device) if want_hidden else None
-    if k_split is not None:
-        if len(k_split) != 4:
-            raise ValueError("tower_forward: k_split is (qkv, out_proj, fc1, fc2)")
-        if pt.probe is not None:
-            raise ValueError("tower_forward: the timing probe goes with k_split=None (slime_vit_forward_ex)")
-        ks = _lib.VitKsplit(*(int(v) for v in k_split))
-        need = lib.slime_vit_ksplit_workspace_bytes(C.byref(pt.desc), n, C.byref(ks))
-        base, avail = pt.ws.aligned(need, pixels.device)
-        if pt.act != _lib.ACT_QUICKGELU:
-            _tower_opts_call(lib, pt, pixels, n, out, out_dtype, keep_cls, hidden, None, ks, base, avail)
-            return (out, hidden) if want_hidden else out
-        _lib.check(lib.slime_vit_forward_ksplit(C.byref(pt.desc), pixels.data_ptr(), dtype_code(pixels.dtype), n, out.data_ptr(),
-                                                dtype_code(out_dtype), int(keep_cls), _ptr(hidden), C.byref(ks), base,
-                                                avail, _stream()), "slime_vit_forward_ksplit")
-        return (out, hidden) if want_hidden else out
-    need = lib.slime_vit_workspace_bytes(C.byref(pt.desc), n)
-    base, avail = pt.ws.aligned(need, pixels.device)
-    if pt.act != _lib.ACT_QUICKGELU:
-        if pt.probe is not None:
-            raise ValueError("tower_forward: the timing probe (slime_vit_forward_ex) is built for quick-GELU towers")
-        _tower_opts_call(lib, pt, pixels, n, out, out_dtype, keep_cls, hidden, None, None, base, avail)
-        return (out, hidden) if want_hidden else out
-    probe = None
-    if pt.probe is not None:
-        layer, kernel, e0, e1 = pt.probe
-        probe = C.byref(_lib.Probe(int(layer), int(kernel), e0.cuda_event, e1.cuda_event))
-    _lib.check(lib.slime_vit_forward_ex(C.byref(pt.desc), pixels.data_ptr(), dtype_code(pixels.dtype), n, out.data_ptr(),
-                                        dtype_code(out_dtype), int(keep_cls), _ptr(hidden), base,
-                                        avail, _stream(), probe), "slime_vit_forward")
+    _tower_call(pt, pixels, out, keep_cls, hidden, None, k_split)
     return (out, hidden) if want_hidden else out
 
 
-def _tower_opts_call(lib, pt: PackedTower, pixels, n, out, out_dtype, keep_cls, hidden, states, ks, base, avail) -> None:
-    """slime_vit_forward_opts with the tower's activation: the one entry that takes it (any of out / hidden / states, optional k-split)."""
-    opts = _lib.VitOpts(pt.act)
-    _lib.check(lib.slime_vit_forward_opts(C.byref(pt.desc), C.byref(opts), pixels.data_ptr(), dtype_code(pixels.dtype), n, _ptr(out),
-                                          dtype_code(out_dtype) if out is not None else _lib.F32, int(keep_cls), _ptr(hidden), _ptr(states),
-                                          C.byref(ks) if ks is not None else None, base, avail, _stream()), "slime_vit_forward_opts")
-
-
-def tower_hidden_states(pt: PackedTower, pixels: torch.Tensor) -> torch.Tensor:
-    """pixels [N,3,S,S] -> fp32 [layers_run + 1, N, 1 + P, D]: every hidden state of ONE tower pass (slime_vit_forward_states)."""
-    lib = _lib.load()
-    _require_cuda(pixels, "pixels")
-    cfg = pt.cfg
-    if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != cfg.image_size or pixels.shape[3] != cfg.image_size:
-        raise ValueError(f"Input image size ({tuple(pixels.shape[2:])}) doesn't match model ({cfg.image_size}*{cfg.image_size}).")
-    if pixels.dtype not in (torch.float32, pt.dtype):
-        pixels = pixels.to(pt.dtype)
-    pixels = pixels.contiguous()
-    n = pixels.shape[0]
-    states = torch.empty((pt.layers_run + 1, n, cfg.seq_len, cfg.hidden_size), dtype=torch.float32, device=pixels.device)
-    need = lib.slime_vit_workspace_bytes(C.byref(pt.desc), n)
-    base, avail = pt.ws.aligned(need, pixels.device)
-    if pt.act != _lib.ACT_QUICKGELU:
-        _tower_opts_call(lib, pt, pixels, n, None, None, True, None, states, None, base, avail)
-        return states
-    _lib.check(lib.slime_vit_forward_states(C.byref(pt.desc), pixels.data_ptr(), dtype_code(pixels.dtype), n, states.data_ptr(), base,
-                                            avail, _stream()), "slime_vit_forward_states")
+def tower_hidden_states(pt: PackedTower, pixels: torch.Tensor, k_split: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """pixels [N,3,S,S] -> fp32 [layers_run + 1, N, cfg.seq_len, D]: HF's hidden_states of ONE tower pass (entry 0 = the embeddings,
+    after the pre-LayerNorm where the tower has one)."""
+    pixels = _tower_pixels(pt, pixels)
+    states = torch.empty((pt.layers_run + 1, pixels.shape[0], pt.cfg.seq_len, pt.cfg.hidden_size), dtype=torch.float32,
+                         device=pixels.device)
+    _tower_call(pt, pixels, None, True, None, states, k_split)
     return states
+
+
+# The family-named calls, kept as spellings of the one path above (existing callers and the SigLIP / DINOv2 GPU tests use them).
+siglip_tower_hidden_states = dinov2_tower_hidden_states = tower_hidden_states
+
+
+def siglip_tower_forward(pt: PackedTower, pixels, out_dtype=None, want_hidden=False, out=None, k_split=None):
+    """``tower_forward`` without ``keep_cls``: a SigLIP tower has no rows in front of its patches."""
+    return tower_forward(pt, pixels, out_dtype, False, want_hidden, out, k_split)
+
+
+def dinov2_tower_forward(pt: PackedTower, pixels, out_dtype=None, keep_prefix=False, want_hidden=False, out=None, k_split=None):
+    """``tower_forward`` with ``keep_cls`` under its DINOv2 name."""
+    return tower_forward(pt, pixels, out_dtype, keep_prefix, want_hidden, out, k_split)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -545,20 +582,6 @@ def tower_hidden_states(pt: PackedTower, pixels: torch.Tensor) -> torch.Tensor:
 # ------------------------------------------------------------------------------------------------
 SIGLIP_ACT = "gelu_pytorch_tanh"
 SIGLIP_MAX_GRID = 24
-
-
-@dataclass
-class PackedSiglipTower:
-    cfg: SiglipVisionConfig
-    dtype: torch.dtype
-    layers_run: int
-    tensors: Dict[str, torch.Tensor]
-    desc: _lib.VitDesc
-    ws: Workspace = field(default_factory=Workspace)
-
-    @property
-    def device(self):
-        return self.tensors["pos"].device
 
 
 def check_siglip_config(cfg: SiglipVisionConfig) -> None:
@@ -583,8 +606,7 @@ def siglip_host_tensors(state_dict: Dict[str, torch.Tensor], cfg: SiglipVisionCo
     """``tower_host_tensors`` for the SigLIP layout: the conv weight as a [D, kpad] matrix, ``pos`` = position_embedding +
     patch_embedding.bias [P, D] (one fp32 addition per element at pack time; float64 with dtype = None), and the same per-layer
     tensors.  ``post_layernorm.*`` and ``head.*`` are not read."""
-    if dtype not in (None, torch.bfloat16, torch.float16):
-        raise ValueError("tower compute dtype must be bf16 or fp16 (MFMA operand type); fp32 I/O is supported")
+    _check_operand_dtype(dtype, allow_none=True)
     sd = strip_tower_prefix(state_dict)
     L = layers_for_select(cfg, select_layer)
     f32, tt = _host_casts(dtype)
@@ -595,76 +617,14 @@ def siglip_host_tensors(state_dict: Dict[str, torch.Tensor], cfg: SiglipVisionCo
 
 
 def pack_siglip_tower(state_dict: Dict[str, torch.Tensor], cfg: SiglipVisionConfig, dtype: torch.dtype, device,
-                      select_layer: int = -2) -> PackedSiglipTower:
+                      select_layer: int = -2) -> PackedTower:
     """HF SiglipVisionModel state dict (either key generation) -> device tensors in the kernels' layout, as ``pack_tower``: LayerNorm
     gamma / beta folded into q/k/v and fc1, pos', the fragment-order images, the colsums; slime_siglip_check at pack time."""
-    if dtype not in (torch.bfloat16, torch.float16):
-        raise ValueError("tower compute dtype must be bf16 or fp16 (MFMA operand type); fp32 I/O is supported")
+    _check_operand_dtype(dtype)
     check_siglip_config(cfg)
     L = layers_for_select(cfg, select_layer)
-    T: Dict[str, torch.Tensor] = {k: v.to(device).contiguous() for k, v in siglip_host_tensors(state_dict, cfg, dtype, select_layer).items()}
-    if L > 0:
-        pack_static(T, ("w_qkv", "w_o", "w_fc1", "w_fc2"))
-    T["patch_w_frag"] = pack_b_frag(T["patch_w"])          # the front end (slime_patch_embed_plain) reads this image only
-    if T["patch_w_frag"] is None:
-        if not T["patch_w"].is_cuda:
-            raise _lib.SlimeHipError("pack_siglip_tower: weights are packed on the GPU (slime_gemm_pack_b): slime_amd has no CPU path")
-        raise ValueError("pack_siglip_tower: the patch-embed weight could not be packed (hidden size must be a multiple of 64)")
-    T["patch_w"] = None
-    d = _vit_desc(T, cfg, dtype, L)
-    _lib.check(_lib.load().slime_siglip_check(C.byref(d)), "pack_siglip_tower")
-    return PackedSiglipTower(cfg, dtype, L, T, d)
-
-
-def _siglip_pixels(pt: PackedSiglipTower, pixels: torch.Tensor) -> torch.Tensor:
-    _require_cuda(pixels, "pixels")
-    cfg = pt.cfg
-    if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != cfg.image_size or pixels.shape[3] != cfg.image_size:
-        raise ValueError(f"Input image size ({tuple(pixels.shape[2:])}) doesn't match model ({cfg.image_size}*{cfg.image_size}).")
-    if pixels.dtype not in (torch.float32, pt.dtype):
-        pixels = pixels.to(pt.dtype)
-    return pixels.contiguous()
-
-
-def _siglip_call(pt: PackedSiglipTower, pixels, out, hidden, states, k_split) -> None:
-    lib = _lib.load()
-    n, ks = pixels.shape[0], None
-    if k_split is not None:
-        if len(k_split) != 4:
-            raise ValueError("siglip_tower_forward: k_split is (qkv, out_proj, fc1, fc2)")
-        ks = _lib.VitKsplit(*(int(v) for v in k_split))
-        need = lib.slime_siglip_ksplit_workspace_bytes(C.byref(pt.desc), n, C.byref(ks))
-    else:
-        need = lib.slime_siglip_workspace_bytes(C.byref(pt.desc), n)
-    base, avail = pt.ws.aligned(need, pixels.device)
-    _lib.check(lib.slime_siglip_forward(C.byref(pt.desc), pixels.data_ptr(), dtype_code(pixels.dtype), n, _ptr(out),
-                                        dtype_code(out.dtype) if out is not None else _lib.F32, _ptr(hidden), _ptr(states),
-                                        C.byref(ks) if ks is not None else None, base, avail, _stream()), "slime_siglip_forward")
-
-
-def siglip_tower_forward(pt: PackedSiglipTower, pixels: torch.Tensor, out_dtype: Optional[torch.dtype] = None,
-                         want_hidden: bool = False, out: Optional[torch.Tensor] = None, k_split: Optional[Sequence[int]] = None):
-    """pixels [N,3,S,S] (fp32 or the tower dtype) -> hidden_states[select_layer] [N, P, D] in out_dtype: all P tokens (written into
-    ``out`` if given).  k_split as in :func:`tower_forward`."""
-    pixels = _siglip_pixels(pt, pixels)
-    cfg, n = pt.cfg, pixels.shape[0]
-    out_dtype = out_dtype or pixels.dtype
-    if out is None:
-        out = torch.empty((n, cfg.num_patches, cfg.hidden_size), dtype=out_dtype, device=pixels.device)
-    elif tuple(out.shape) != (n, cfg.num_patches, cfg.hidden_size) or out.dtype != out_dtype or not out.is_contiguous():
-        raise ValueError("siglip_tower_forward: out must be a contiguous [N, P, hidden] tensor of the output dtype")
-    hidden = torch.empty((n, cfg.num_patches, cfg.hidden_size), dtype=torch.float32, device=pixels.device) if want_hidden else None
-    _siglip_call(pt, pixels, out, hidden, None, k_split)
-    return (out, hidden) if want_hidden else out
-
-
-def siglip_tower_hidden_states(pt: PackedSiglipTower, pixels: torch.Tensor, k_split: Optional[Sequence[int]] = None) -> torch.Tensor:
-    """pixels [N,3,S,S] -> fp32 [layers_run + 1, N, P, D]: HF's hidden_states of ONE tower pass (entry 0 = the embeddings)."""
-    pixels = _siglip_pixels(pt, pixels)
-    states = torch.empty((pt.layers_run + 1, pixels.shape[0], pt.cfg.num_patches, pt.cfg.hidden_size), dtype=torch.float32,
-                         device=pixels.device)
-    _siglip_call(pt, pixels, None, None, states, k_split)
-    return states
+    return _pack_tail("pack_siglip_tower", "siglip", siglip_host_tensors(state_dict, cfg, dtype, select_layer), cfg, dtype, device, L,
+                      lambda lib, d: lib.slime_siglip_check(d))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -674,20 +634,6 @@ DINOV2_ACT = "gelu"
 DINOV2_MAX_GRID = 24
 DINOV2_MAX_REGISTERS = 16
 DINOV2_WIDTHS = (128, 256, 768, 1024)
-
-
-@dataclass
-class PackedDinov2Tower:
-    cfg: Dinov2VisionConfig
-    dtype: torch.dtype
-    layers_run: int
-    tensors: Dict[str, torch.Tensor]
-    desc: _lib.VitDesc
-    ws: Workspace = field(default_factory=Workspace)
-
-    @property
-    def device(self):
-        return self.tensors["pos"].device
 
 
 def check_dinov2_config(cfg: Dinov2VisionConfig) -> None:
@@ -749,17 +695,14 @@ def dinov2_host_tensors(state_dict: Dict[str, torch.Tensor], cfg: Dinov2VisionCo
     fp16 and small lambda: a folded weight lambda * w below 2^-14 lands on the fp16 subnormal grid (spacing 2^-24), so its absolute
     rounding error is at most 2^-25 instead of 2^-11 relative; over a row of the GEMM that moves an element of h by at most
     2^-25 * sum_k |a_k|.  bf16 has fp32's exponent range and keeps its relative 2^-8."""
-    if dtype not in (None, torch.bfloat16, torch.float16):
-        raise ValueError("tower compute dtype must be bf16 or fp16 (MFMA operand type); fp32 I/O is supported")
+    _check_operand_dtype(dtype, allow_none=True)
     sd = strip_dinov2_prefix(state_dict)
     if image_size is not None and image_size != cfg.image_size:
         cfg = dataclasses.replace(cfg, image_size=int(image_size))
     L = layers_for_select(cfg, select_layer)
     f32, tt = _host_casts(dtype)
-    D, R, P2 = cfg.hidden_size, cfg.num_register_tokens, 3 * cfg.patch_size * cfg.patch_size
+    D, R = cfg.hidden_size, cfg.num_register_tokens
     e = "embeddings."
-    pw = torch.zeros((D, (P2 + 63) // 64 * 64), dtype=torch.float32)
-    pw[:, :P2] = sd[e + "patch_embeddings.projection.weight"].detach().float().cpu().reshape(D, P2)
     table = sd[e + "position_embeddings"]
     prefix = [f32(sd[e + "cls_token"]).reshape(1, D) + f32(table)[0, :1]]
     if R > 0:
@@ -768,115 +711,24 @@ def dinov2_host_tensors(state_dict: Dict[str, torch.Tensor], cfg: Dinov2VisionCo
             raise ValueError(f"DINOv2 checkpoint has {regs.shape[0]} register tokens, the config says {R}")
         prefix.append(regs)
     pos = f32(dinov2_pos_table(table, cfg.grid, cfg.antialias)) + f32(sd[e + "patch_embeddings.projection.bias"])[None, :]
-    T: Dict[str, torch.Tensor] = {"patch_w": tt(pw), "cls": torch.cat(prefix, 0).contiguous(), "pos": pos.contiguous()}
-    if L > 0:
-        rs = torch.ones(3 * D, dtype=torch.float64)
-        rs[:D] = cfg.head_dim ** -0.5 * LOG2E                  # q rows carry dh^-0.5 * log2 e (slime_attention contract)
-        cols = {k: [] for k in ("w_qkv", "b_qkv", "colsum_qkv", "w_fc1", "b_fc1", "colsum_fc1", "w_o", "b_o", "w_fc2", "b_fc2")}
-        for i in range(L):
-            q = f"encoder.layer.{i}."
-            a = q + "attention.attention."
-            Wm = torch.cat([sd[a + "query.weight"].float(), sd[a + "key.weight"].float(), sd[a + "value.weight"].float()], 0)
-            bm = torch.cat([sd[a + "query.bias"].float(), sd[a + "key.bias"].float(), sd[a + "value.bias"].float()], 0)
-            for k, v in zip(("w_qkv", "b_qkv", "colsum_qkv"), fold_ln(Wm, bm, sd[q + "norm1.weight"], sd[q + "norm1.bias"], rs, dtype)):
-                cols[k].append(v)
-            for k, v in zip(("w_fc1", "b_fc1", "colsum_fc1"),
-                            fold_ln(sd[q + "mlp.fc1.weight"], sd[q + "mlp.fc1.bias"], sd[q + "norm2.weight"], sd[q + "norm2.bias"], None, dtype)):
-                cols[k].append(v)
-            for w, b, lin, lam in (("w_o", "b_o", q + "attention.output.dense", q + "layer_scale1.lambda1"),
-                                   ("w_fc2", "b_fc2", q + "mlp.fc2", q + "layer_scale2.lambda1")):
-                s = sd[lam].detach().double().cpu()            # output feature j of the Linear is scaled by lambda[j]: row j of W, b[j]
-                cols[w].append(tt(sd[lin + ".weight"].detach().double().cpu() * s[:, None]))
-                cols[b].append(f32(sd[lin + ".bias"].detach().double().cpu() * s))
-        for k, v in cols.items():
-            T[k] = torch.stack(v).contiguous()
+    T: Dict[str, torch.Tensor] = {"patch_w": _conv_matrix(sd, cfg, tt, e + "patch_embeddings.projection.weight"),
+                                  "cls": torch.cat(prefix, 0).contiguous(), "pos": pos.contiguous()}
+    _layer_host_tensors(T, sd, cfg, dtype, L, DINOV2_LAYER_KEYS)
     return T
 
 
 def pack_dinov2_tower(state_dict: Dict[str, torch.Tensor], cfg: Dinov2VisionConfig, dtype: torch.dtype, device,
-                      select_layer: int = -2, image_size: Optional[int] = None) -> PackedDinov2Tower:
+                      select_layer: int = -2, image_size: Optional[int] = None) -> PackedTower:
     """HF Dinov2Model / Dinov2WithRegistersModel state dict -> device tensors in the kernels' layout, as ``pack_tower``
-    (``dinov2_host_tensors`` on ``device``, the fragment-order images); slime_dinov2_check at pack time."""
-    if dtype not in (torch.bfloat16, torch.float16):
-        raise ValueError("tower compute dtype must be bf16 or fp16 (MFMA operand type); fp32 I/O is supported")
+    (``dinov2_host_tensors`` on ``device``, the fragment-order images); slime_dinov2_check at pack time.  In the descriptor ``image``
+    is the run size, ``cls`` the prefix table, and ``pre_ln_*`` stay NULL."""
+    _check_operand_dtype(dtype)
     if image_size is not None and image_size != cfg.image_size:
         cfg = dataclasses.replace(cfg, image_size=int(image_size))
     check_dinov2_config(cfg)
     L = layers_for_select(cfg, select_layer)
-    T: Dict[str, torch.Tensor] = {k: v.to(device).contiguous() for k, v in dinov2_host_tensors(state_dict, cfg, dtype, select_layer).items()}
-    if L > 0:
-        pack_static(T, ("w_qkv", "w_o", "w_fc1", "w_fc2"))
-    T["patch_w_frag"] = pack_b_frag(T["patch_w"])          # the front end (slime_patch_embed_prefix) reads this image only
-    if T["patch_w_frag"] is None:
-        if not T["patch_w"].is_cuda:
-            raise _lib.SlimeHipError("pack_dinov2_tower: weights are packed on the GPU (slime_gemm_pack_b): slime_amd has no CPU path")
-        raise ValueError("pack_dinov2_tower: the patch-embed weight could not be packed (hidden size must be a multiple of 64)")
-    T["patch_w"] = None
-    d = dinov2_desc(T, cfg, dtype, L)
-    _lib.check(_lib.load().slime_dinov2_check(C.byref(d), cfg.n_prefix), "pack_dinov2_tower")
-    return PackedDinov2Tower(cfg, dtype, L, T, d)
-
-
-def dinov2_desc(T: Dict[str, Optional[torch.Tensor]], cfg: Dinov2VisionConfig, dtype: torch.dtype, L: int) -> "_lib.VitDesc":
-    """slime_vit_desc of a DINOv2 tower: ``image`` is the run size, ``cls`` the prefix table, ``pre_ln_*`` stay NULL."""
-    return _vit_desc(T, SimpleNamespace(hidden_size=cfg.hidden_size, intermediate_size=cfg.intermediate_size,
-                                        num_attention_heads=cfg.num_attention_heads, image_size=cfg.image_size, patch_size=cfg.patch_size,
-                                        layer_norm_eps=cfg.layer_norm_eps), dtype, L)
-
-
-def _dinov2_pixels(pt: PackedDinov2Tower, pixels: torch.Tensor) -> torch.Tensor:
-    _require_cuda(pixels, "pixels")
-    s = pt.cfg.image_size
-    if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != s or pixels.shape[3] != s:
-        raise ValueError(f"Input image size ({tuple(pixels.shape[2:])}) doesn't match the size the tower was packed for ({s}*{s}).")
-    if pixels.dtype not in (torch.float32, pt.dtype):
-        pixels = pixels.to(pt.dtype)
-    return pixels.contiguous()
-
-
-def _dinov2_call(pt: PackedDinov2Tower, pixels, out, keep_prefix, hidden, states, k_split) -> None:
-    lib = _lib.load()
-    n, ks, npre = pixels.shape[0], None, pt.cfg.n_prefix
-    if k_split is not None:
-        if len(k_split) != 4:
-            raise ValueError("dinov2_tower_forward: k_split is (qkv, out_proj, fc1, fc2)")
-        ks = _lib.VitKsplit(*(int(v) for v in k_split))
-        need = lib.slime_dinov2_ksplit_workspace_bytes(C.byref(pt.desc), npre, n, C.byref(ks))
-    else:
-        need = lib.slime_dinov2_workspace_bytes(C.byref(pt.desc), npre, n)
-    base, avail = pt.ws.aligned(need, pixels.device)
-    _lib.check(lib.slime_dinov2_forward(C.byref(pt.desc), npre, pixels.data_ptr(), dtype_code(pixels.dtype), n, _ptr(out),
-                                        dtype_code(out.dtype) if out is not None else _lib.F32, int(bool(keep_prefix)), _ptr(hidden),
-                                        _ptr(states), C.byref(ks) if ks is not None else None, base, avail, _stream()),
-               "slime_dinov2_forward")
-
-
-def dinov2_tower_forward(pt: PackedDinov2Tower, pixels: torch.Tensor, out_dtype: Optional[torch.dtype] = None,
-                         keep_prefix: bool = False, want_hidden: bool = False, out: Optional[torch.Tensor] = None,
-                         k_split: Optional[Sequence[int]] = None):
-    """pixels [N,3,S,S] (fp32 or the tower dtype) -> hidden_states[select_layer] in out_dtype: the P patch rows [N, P, D], or with
-    ``keep_prefix`` all n_prefix + P rows (class token, registers, patches).  ``want_hidden`` adds the fp32 state with all rows.
-    k_split as in :func:`tower_forward`."""
-    pixels = _dinov2_pixels(pt, pixels)
-    cfg, n = pt.cfg, pixels.shape[0]
-    out_dtype = out_dtype or pixels.dtype
-    rows = cfg.seq_len if keep_prefix else cfg.num_patches
-    if out is None:
-        out = torch.empty((n, rows, cfg.hidden_size), dtype=out_dtype, device=pixels.device)
-    elif tuple(out.shape) != (n, rows, cfg.hidden_size) or out.dtype != out_dtype or not out.is_contiguous():
-        raise ValueError("dinov2_tower_forward: out must be a contiguous [N, rows, hidden] tensor of the output dtype")
-    hidden = torch.empty((n, cfg.seq_len, cfg.hidden_size), dtype=torch.float32, device=pixels.device) if want_hidden else None
-    _dinov2_call(pt, pixels, out, keep_prefix, hidden, None, k_split)
-    return (out, hidden) if want_hidden else out
-
-
-def dinov2_tower_hidden_states(pt: PackedDinov2Tower, pixels: torch.Tensor, k_split: Optional[Sequence[int]] = None) -> torch.Tensor:
-    """pixels [N,3,S,S] -> fp32 [layers_run + 1, N, n_prefix + P, D]: HF's hidden_states of ONE tower pass (entry 0 = the embeddings)."""
-    pixels = _dinov2_pixels(pt, pixels)
-    states = torch.empty((pt.layers_run + 1, pixels.shape[0], pt.cfg.seq_len, pt.cfg.hidden_size), dtype=torch.float32,
-                         device=pixels.device)
-    _dinov2_call(pt, pixels, None, True, None, states, k_split)
-    return states
+    return _pack_tail("pack_dinov2_tower", "dinov2", dinov2_host_tensors(state_dict, cfg, dtype, select_layer), cfg, dtype, device, L,
+                      lambda lib, d: lib.slime_dinov2_check(d, cfg.n_prefix))
 
 
 def gemm_kernel_name(M: int, N: int, K: int, dtype: torch.dtype, epilogue: int, has_b_frag: bool = False) -> str:
@@ -893,9 +745,13 @@ def tower_kernel_names(pt: PackedTower, n_crops: int) -> Dict[int, str]:
     t = "F16" if pt.dtype == torch.float16 else "BF16"
     fr = {k: pt.tensors.get(k + "_frag") is not None for k in ("w_qkv", "w_o", "w_fc1", "w_fc2")}
     resid_epi = _lib.load().slime_vit_residual_epilogue()      # what the tower launches for out_proj / fc2
+    if pt.form == "siglip":
+        fc1_epi = _lib.EPI_BIAS_GELU_TANH_T
+    else:
+        fc1_epi = _lib.EPI_BIAS_GELU_T if pt.form == "dinov2" or pt.act == _lib.ACT_GELU else _lib.EPI_BIAS_QUICKGELU_T
     return {1: gemm_kernel_name(M, 3 * D, D, pt.dtype, _lib.EPI_BIAS_T, fr["w_qkv"]),
             2: f"attn64r_kernel<{t}, 3>" if 321 <= cfg.seq_len <= 608 and cfg.head_dim == 64 else f"attn_kernel<{t}, 64, 608, 8, 5>",
-            5: gemm_kernel_name(M, Fi, D, pt.dtype, _lib.EPI_BIAS_GELU_T if pt.act == _lib.ACT_GELU else _lib.EPI_BIAS_QUICKGELU_T, fr["w_fc1"]),
+            5: gemm_kernel_name(M, Fi, D, pt.dtype, fc1_epi, fr["w_fc1"]),
             3: gemm_kernel_name(M, D, D, pt.dtype, resid_epi, fr["w_o"]),
             6: gemm_kernel_name(M, D, Fi, pt.dtype, resid_epi, fr["w_fc2"])}
 
