@@ -390,7 +390,10 @@ int slime_view_jobs(const slime_view_job* jobs_host, const slime_view_job* jobs_
 
 /* Text-guided router, scores (TextGuidedRouterCosine.forward, resampler/builder.py:186-201):
  * scores[t] = sum_l mask[l] * cos(img[t], text[l]) (mean over l if mask is NULL); img fp32 [T,H], text fp32
- * [L,H], mask uint8 [L]; ws: L+H+4 floats of scratch. */
+ * [L,H], mask uint8 [L]; ws: L + H + 4 floats of scratch.  H is a multiple of 4; img, text and ws must be 16-byte aligned
+ * (16-byte loads), scores 4-byte aligned: anything else is refused with SLIME_EINVAL before a launch.
+ * Precondition: text must be finite, masked rows included -- a masked-out row enters as 0 * text[l], which only a finite
+ * value leaves at 0 (the reference ignores what such a row holds).  Each operand is normalised with max(|x|, 1e-8f) on its own. */
 int slime_router_scores(const float* img, int T, const float* text, int L, const unsigned char* mask, int H,
                         float* scores, float* ws, void* stream);
 
@@ -405,7 +408,9 @@ int slime_router_select(const float* scores, int T, float temp, float topp, int*
  * image b owns rows row_off[b] .. row_off[b] + n_rows[b] - 1 of img (row_off int64 / n_rows int32, DEVICE arrays -- the
  * local-token rows of a fused [B, 576 + T, H] token buffer or a ragged concatenation); text fp32 [B, L, H], mask uint8
  * [B, L] or NULL; scores / keep_idx are padded [B, T_max], keep_count [B]: ONE D2H read of keep_count serves the batch.
- * ws: slime_router_batched_workspace_floats(B, L, H) floats. */
+ * ws: slime_router_batched_workspace_floats(B, L, H) floats.  As for the single entry: img, text and ws must be 16-byte aligned
+ * and scores 4-byte aligned, else SLIME_EINVAL before a launch; text must be finite, masked rows included.  Elements of
+ * scores at or behind n_rows[b] in row b are not written. */
 size_t slime_router_batched_workspace_floats(int B, int L, int H);
 int slime_router_scores_batched(const float* img, const long long* row_off, const int* n_rows, int B, int T_max,
                                 const float* text, int L, const unsigned char* mask, int H, float* scores, float* ws,

@@ -8,7 +8,8 @@
 // which turns a [T x L x H] contraction into two HBM-bound passes (L*H + T*H reads).
 // The selection (softmax / temperature, descending sort, cumulative sum, "<= top-p plus one",
 // ascending re-sort) runs in ONE workgroup with the sorted list in LDS; the cumulative sum is
-// evaluated sequentially in sort order like torch's CPU cumsum.
+// evaluated sequentially in sort order, every partial sum rounded to fp32 (torch's CPU cumsum walks
+// the same order but carries a double, so it can sit one ulp away at a sum that lands on top-p).
 #include "common.h"
 
 // w[l] = mask[l] / max(|text[l]|, eps)   (one wave per text token)
@@ -161,8 +162,12 @@ __global__ void __launch_bounds__(1024) router_select_kernel(const float* scores
 }
 
 extern "C" int slime_router_scores(const float* img, int T, const float* text, int L, const unsigned char* mask, int H,
-                                   float* scores, float* ws /* L + H floats */, void* stream) {
-    SLIME_REQUIRE(img && text && scores && ws && T > 0 && L > 0 && H % 4 == 0, "router_scores: bad input");
+                                   float* scores, float* ws /* L + H + 4 floats */, void* stream) {
+    SLIME_REQUIRE(img && text && scores && ws && T > 0 && L > 0 && H > 0 && H % 4 == 0, "router_scores: bad input");
+    SLIME_REQUIRE(((uintptr_t)img % 16) == 0, "router_scores: img must be 16-byte aligned");
+    SLIME_REQUIRE(((uintptr_t)text % 16) == 0, "router_scores: text must be 16-byte aligned");
+    SLIME_REQUIRE(((uintptr_t)ws % 16) == 0, "router_scores: ws must be 16-byte aligned");
+    SLIME_REQUIRE(((uintptr_t)scores % 4) == 0, "router_scores: scores must be 4-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     float* w = ws;
     float* u = ws + ((L + 3) / 4 * 4);
@@ -195,8 +200,12 @@ extern "C" size_t slime_router_batched_workspace_floats(int B, int L, int H) {
 extern "C" int slime_router_scores_batched(const float* img, const long long* row_off, const int* n_rows, int B, int T_max,
                                            const float* text, int L, const unsigned char* mask, int H, float* scores,
                                            float* ws, void* stream) {
-    SLIME_REQUIRE(img && row_off && n_rows && text && scores && ws && B > 0 && B <= 65535 && T_max > 0 && L > 0 && H % 4 == 0,
+    SLIME_REQUIRE(img && row_off && n_rows && text && scores && ws && B > 0 && B <= 65535 && T_max > 0 && L > 0 && H > 0 && H % 4 == 0,
                   "router_scores_batched: bad input");
+    SLIME_REQUIRE(((uintptr_t)img % 16) == 0, "router_scores_batched: img must be 16-byte aligned");
+    SLIME_REQUIRE(((uintptr_t)text % 16) == 0, "router_scores_batched: text must be 16-byte aligned");
+    SLIME_REQUIRE(((uintptr_t)ws % 16) == 0, "router_scores_batched: ws must be 16-byte aligned");
+    SLIME_REQUIRE(((uintptr_t)scores % 4) == 0, "router_scores_batched: scores must be 4-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const int per = (L + 3) / 4 * 4 > H ? (L + 3) / 4 * 4 : H;     // one stride for the w [L] and u [H] tables of an image
     float* w = ws;
