@@ -91,7 +91,15 @@ int slime_gemm(const void* A, int lda, const void* B, const float* bias, void* C
  *     with mu / rstd = rsqrt(var + ln_eps) from the ln_groups partial sums of each row (K = the normalised width), then the
  *     epilogue's activation on that pre-activation (BIAS_GELU_T: the erf form of the un-folded epilogue, for towers whose
  *     hidden_act is 'gelu').
- * Identical to LayerNorm followed by the GEMM up to rounding (x is rounded to T before instead of after the normalisation). */
+ * Identical to LayerNorm followed by the GEMM up to rounding (x is rounded to T before instead of after the normalisation).
+ *
+ * LIMIT on lda (slime_gemm, slime_gemm_ex and slime_gemm_ksplit; A and A2): the product library's kernels keep a lane's A offset relative to its tile
+ * of up to SLIME_GEMM_MAX_TILE_ROWS rows in a 32-bit register, so (SLIME_GEMM_MAX_TILE_ROWS - 1) * lda * 2 + K * 2 must not exceed
+ * 2^32 bytes: any lda <= 2^23 elements (16 MiB rows) is accepted, a larger one is refused with SLIME_EINVAL and the limit named in
+ * slime_last_error().  The tile's base and every other operand (C / ldc, x16 / ldx, resid / ldr, lo8 / ldlo, row_map) are addressed
+ * in 64 bits: M * lda, M * ldc, ... may exceed 2^32 bytes.  (One measured alternative of the diagnostic build, gemm_ppp_kernel, uses
+ * the absolute row in 32 bits; the diagnostic dispatch hands it only calls with M * lda * 2 < 2^32 and falls back otherwise.) */
+#define SLIME_GEMM_MAX_TILE_ROWS 256
 typedef struct {
     const void* A; int lda; const void* B; const float* bias; void* C; int ldc;
     int M, N, K, dtype, epilogue;

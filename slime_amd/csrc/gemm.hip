@@ -1546,6 +1546,15 @@ static int gemm_check_args(const slime_gemm_args* a, GemmArgs& out) {
     SLIME_REQUIRE(K % 64 == 0, "gemm: K=%d must be a multiple of 64", K);
     SLIME_REQUIRE(N % 128 == 0, "gemm: N=%d must be a multiple of 128", N);
     SLIME_REQUIRE(lda >= K && lda % 8 == 0 && ldc >= N && ldc % 8 == 0, "gemm: bad leading dims lda=%d ldc=%d", lda, ldc);
+    // every kernel family (lock-step, ping-pong, w4, direct-B, k-split) keeps the A offsets of a lane RELATIVE TO ITS TILE -- row in
+    // tile x lda x 2 bytes, plus the position in the k range -- in 32-bit registers; the tallest tile has SLIME_GEMM_MAX_TILE_ROWS rows.
+    // ONE EXCEPTION, in the diagnostic build only: gemm_ppp_kernel (gemm_diag.inc, forced tile 5) multiplies the ABSOLUTE row by lda in
+    // 32 bits, which this limit does not cover; its own rule in launch_epi (M * lda * 2 < 2^32, else tile 4) is what protects it and
+    // is NOT redundant with the check below.
+    const unsigned long long a_reach = (unsigned long long)(SLIME_GEMM_MAX_TILE_ROWS - 1) * (unsigned long long)lda * 2ull + (unsigned long long)K * 2ull;
+    SLIME_REQUIRE(a_reach <= (1ull << 32),
+                  "gemm: lda=%d is too large: the tile-relative byte offset (%d - 1) * lda * 2 + K * 2 = %llu must fit 32 bits (<= 4294967296); "
+                  "any lda <= 8388608 (2^23) with K < lda does", lda, SLIME_GEMM_MAX_TILE_ROWS, a_reach);
     SLIME_REQUIRE(a->B || (slime_gemm_b_frag_usable(N, K) && ((uintptr_t)a->B_frag % 16) == 0),
                   "gemm: B = NULL needs a fragment-order image this shape can run from (slime_gemm_b_frag_usable)");
     SLIME_REQUIRE(((uintptr_t)a->A % 16 == 0) && ((uintptr_t)a->B % 16 == 0) && ((uintptr_t)a->C % 16 == 0) &&
@@ -1573,8 +1582,9 @@ static int gemm_check_args(const slime_gemm_args* a, GemmArgs& out) {
     if (a->epilogue == SLIME_EPI_BIAS_RESID_T)
         SLIME_REQUIRE(a->resid && a->ldr >= N && a->ldr % 8 == 0 && ((uintptr_t)a->resid % 16) == 0,
                       "gemm: BIAS_RESID_T needs resid T [M, ldr >= N] (16-byte aligned, ldr a multiple of 8)");
-    // the fragment-order copy of B is optional; it is only usable with whole 64-column tiles, >= 2 k-steps per tile and 32-bit A offsets
-    const bool frag_ok = a->B_frag && N % 256 == 0 && ((uintptr_t)a->B_frag % 16) == 0 && (size_t)128 * lda * 2 < (1ull << 32);
+    // the fragment-order copy of B is optional; it is only usable with whole 64-column tiles and >= 2 k-steps per tile (the 32-bit A
+    // offsets of the direct-B kernel's 128-row tile are covered by the lda limit above)
+    const bool frag_ok = a->B_frag && N % 256 == 0 && ((uintptr_t)a->B_frag % 16) == 0;
     if (a->epilogue == SLIME_EPI_BIAS_GELU_MIX_T)
         SLIME_REQUIRE(frag_ok && a->A2 && a->mix_gates && ((uintptr_t)a->A2 % 16) == 0 && ((uintptr_t)a->mix_gates % 8) == 0 && !a->ln_stats,
                       "gemm: BIAS_GELU_MIX_T runs on the direct-B kernel only: needs B_frag (N %% 256 == 0), A2 [M, lda] and mix_gates [M, 2]");

@@ -325,6 +325,7 @@ def test_null_bias(dev, ratios, form, dtype):
 def _refusals():
     yield "lda < K", "bias_t", 256, lambda c, f: dict(lda=c.K - 8), "leading dims"
     yield "ldc % 8 != 0", "bias_t", 256, lambda c, f: dict(ldc=c.N + 4), "leading dims"
+    yield "lda past the tiles' 32-bit A offsets", "bias_t", 256, lambda c, f: dict(lda=1 << 24), "lda=16777216 is too large"
     yield "A off 16-byte alignment", "bias_t", 256, lambda c, f: dict(A=c.buf["A"].ptr() + 2), "16-byte aligned"
     yield "C off 16-byte alignment", "bias_f32", 256, lambda c, f: dict(C=c.buf["C"].ptr() + 4), "16-byte aligned"
     yield "row_map with a residual epilogue", "resid_t", 256, lambda c, f: dict(row_map=c.buf["A"].ptr()), "row_map goes with"
