@@ -764,6 +764,23 @@ int slime_prefill_attention(const void* q, long q_bs, long q_rs, const void* k, 
                             long v_bs, long v_rs, void* o, long o_bs, long o_rs, int batch, int n_heads, int n_kv_heads,
                             int head_dim, int S, const int32_t* kv_start, const int32_t* kv_len, int dtype, void* stream);
 
+/* slime_prefill_attention with a sliding window (MistralAttention / MixtralAttention with config.sliding_window = window):
+ * query row i of sequence b sees key row j iff  j <= i,  i - j < window  (window keys, itself included), and both rows lie in
+ * the token range [kv_start[b], kv_start[b] + kv_len[b]).  Rows are indices into the [batch, S] layout, not position ids.
+ * Output rows outside the token range are zero.
+ *   window == 0       no window: exactly the launches of slime_prefill_attention, bit-identical results.
+ *   window >= S       hides no key: dispatched to the unwindowed kernels as well, bit-identical to slime_prefill_attention.
+ *   0 < window < S    the windowed instantiation of the kernel the unwindowed call takes: prefill32_kernel for group 4 / bf16
+ *                     (Mistral-7B, Mixtral: a 64-row item starts at the first 32-key step its first row can see), the eight-wave
+ *                     kernel for every other group size (1, 2, 8, 16; 4 in fp16) and type (a workgroup starts there likewise, and a
+ *                     wave skips the steps wholly in front of its rows' windows).
+ *   window < 0        SLIME_EINVAL, the value named, before any launch.
+ * Every other argument and refusal as slime_prefill_attention (one implementation behind both). */
+int slime_prefill_attention_window(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v,
+                                   long v_bs, long v_rs, void* o, long o_bs, long o_rs, int batch, int n_heads, int n_kv_heads,
+                                   int head_dim, int S, const int32_t* kv_start, const int32_t* kv_len, int dtype, int window,
+                                   void* stream);
+
 /* LlamaAttention.forward as patched by llava/train/llama_flash_attn_monkey_patch.py:16-93 (no KV cache: prefill). */
 typedef struct {
     int hidden, n_heads, n_kv_heads, head_dim, dtype;
@@ -788,6 +805,15 @@ int slime_llama_attn_forward(const slime_llama_attn_desc* d, const void* hidden,
 int slime_llama_attn_forward_resid(const slime_llama_attn_desc* d, const void* hidden, const int32_t* position_ids,
                                    const int32_t* kv_start, const int32_t* kv_len, int batch, int S, const void* resid,
                                    void* out, void* ws, size_t ws_bytes, void* stream);
+
+/* The same sub-layer with a sliding window in its attention (MistralAttention / MixtralAttention: same projections without
+ * biases, same default rotary embedding): `window` as in slime_prefill_attention_window -- 0 or >= S gives the launches and the
+ * bits of the entries above, < 0 is SLIME_EINVAL before any launch.  resid != NULL: slime_llama_attn_forward_resid (out_dtype
+ * must be the operand type; out may alias resid, not hidden); resid == NULL: slime_llama_attn_forward (out_dtype the operand
+ * type or SLIME_F32).  Workspace: slime_llama_attn_workspace_bytes, unchanged. */
+int slime_llama_attn_forward_window(const slime_llama_attn_desc* d, const void* hidden, const int32_t* position_ids,
+                                    const int32_t* kv_start, const int32_t* kv_len, int batch, int S, const void* resid,
+                                    void* out, int out_dtype, int window, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Measurement aid (bench.py; no reference counterpart)

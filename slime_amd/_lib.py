@@ -234,11 +234,16 @@ _SIGNATURES = {
     "slime_rope": (c_int, [c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_float, c_int, c_void_p]),
     "slime_prefill_attention": (c_int, [c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_void_p, c_long,
                                         c_long, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "slime_prefill_attention_window": (c_int, [c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_void_p,
+                                               c_long, c_long, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                                               c_void_p]),
     "slime_llama_attn_workspace_bytes": (c_size_t, [_P(LlamaAttnDesc), c_int, c_int]),
     "slime_llama_attn_forward": (c_int, [_P(LlamaAttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                                          c_void_p, c_size_t, c_void_p]),
     "slime_llama_attn_forward_resid": (c_int, [_P(LlamaAttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                                c_void_p, c_size_t, c_void_p]),
+    "slime_llama_attn_forward_window": (c_int, [_P(LlamaAttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                                c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
 }
 
 # diagnostic build only (libslime_hip_diag.so): process-global hooks, never exported by the product library

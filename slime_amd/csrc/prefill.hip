@@ -21,6 +21,9 @@
 //                            of the K / V chunk in LDS (repeat_kv never materialises); rows outside the token range are zero.
 //   slime_llama_attn_forward the LlamaAttention.forward of the monkey patch (:16-93): fused q/k/v projection GEMM, RoPE, the
 //                            attention above, o_proj GEMM.
+//   slime_prefill_attention_window / slime_llama_attn_forward_window
+//                            the same two with a sliding window (MistralAttention / MixtralAttention: query i sees keys
+//                            i - W < j <= i): the WIN instantiations of both kernels; window 0 or >= S is the entries above.
 //
 // The attention kernel follows attention.hip's transposed formulation (S^T = K Q^T, O^T = V^T P^T: a lane owns one query
 // column, softmax statistics are lane-local, P never touches LDS) with K/V chunks of 192 rows staged through registers
@@ -328,6 +331,7 @@ struct PrefillArgs {
     const int* kv_start; const int* kv_len;     // per sequence token range, or NULL: [0, S)
     int S, group;
     int n_kv_heads, batch;                      // prefill32_kernel's item space (its grid is a number of workgroups, not of items)
+    int window;                                 // sliding window W >= 1, read by the WIN instantiations only (0 elsewhere)
 #ifdef SLIME_DIAG
     unsigned long long* dbg;                    // 8 counters, or NULL (prefill32.inc)
 #endif
@@ -355,7 +359,12 @@ __device__ __forceinline__ u32x2 lds_tr16(const char* p) {
     return __builtin_bit_cast(u32x2, r);
 }
 
-template <typename T>
+// WIN: the sliding-window variant (Mistral / Mixtral): query row i sees key row j iff j <= i and i - j < a.window, rows being
+// indices into [B, S].  The window is the token range's lower bound made per query row: the workgroup starts at the first
+// step its first row can see, a wave skips the steps wholly in front of its own rows' windows (the mirror of the causal
+// break at the other end), and the element mask gains the window edge.  Rows that have met no live key yet ride on the
+// -1e30 floor of the running maximum exactly as left-padding rows do.  WIN = false compiles the code below unchanged.
+template <typename T, bool WIN = false>
 __global__ void __launch_bounds__(512) prefill_attn_kernel(PrefillArgs a) {
     constexpr int DH = 128, RB = 256, CPR = 16, KS = 4, DT = 8, KC = 192, NW = 8, NSUB = 2, NT = NW * 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -382,6 +391,7 @@ __global__ void __launch_bounds__(512) prefill_attn_kernel(PrefillArgs a) {
     const int q_lo = qb * QB, q_hi = min(q_lo + QB, a.S);     // this workgroup's query rows [q_lo, q_hi)
     const int kv_hi = min(ke_, q_hi);                         // causal: no key beyond the last query row
     const int wave_q_last = max(row0[0], row0[1]) + 15;
+    const int wave_q_first = min(row0[0], row0[1]);
 
     u32x4 qf[NSUB][KS];
 #pragma unroll
@@ -416,7 +426,8 @@ __global__ void __launch_bounds__(512) prefill_attn_kernel(PrefillArgs a) {
     const char* kbase = a.k + ((size_t)b * a.k_bs + (size_t)kvh * DH) * 2;
     const char* vbase = a.v + ((size_t)b * a.v_bs + (size_t)kvh * DH) * 2;
 
-    const int kv_first = (ks_ >> 5) << 5;                     // 32-aligned first step that holds a token
+    int kv_first = (ks_ >> 5) << 5;                           // 32-aligned first step that holds a token
+    if constexpr (WIN) kv_first = (max(ks_, q_lo - a.window + 1) >> 5) << 5;     // ... that the block's first row can see
     // K/V chunk staging, split (issue early / write late): the global loads of chunk c+1 are issued BEFORE the arithmetic of
     // chunk c and held in registers (9 + 9 x 16 B per lane); they are written to LDS, swizzled, after it.  HBM/L2 latency
     // passes under the MFMAs instead of in front of them.
@@ -458,6 +469,9 @@ __global__ void __launch_bounds__(512) prefill_attn_kernel(PrefillArgs a) {
         for (int st = 0; st < steps; ++st) {
             const int kvs = kv0 + st * 32;                    // first key of this step
             if (kvs > wave_q_last) break;                     // causal: nothing left for this wave's queries (wave-uniform)
+            if constexpr (WIN) {
+                if (kvs + 31 < wave_q_first - a.window + 1) continue;   // wholly in front of every row's window (wave-uniform)
+            }
             const char* kp = Klds + st * 32 * RB;
             const char* vp = Vlds + st * 32 * RB;
             f32x4 sc[NSUB][2];
@@ -472,7 +486,9 @@ __global__ void __launch_bounds__(512) prefill_attn_kernel(PrefillArgs a) {
                     for (int s = 0; s < NSUB; ++s) sc[s][t] = T::mfma16(kf, qf[s][ks], sc[s][t]);
                 }
             // masks: causal (key > query), token range.  Steps strictly inside [ks_, min(row0) ] need none (wave-uniform test).
-            if (kvs + 31 > min(row0[0], row0[1]) || kvs < ks_ || kvs + 32 > kv_hi) {
+            bool masked = kvs + 31 > wave_q_first || kvs < ks_ || kvs + 32 > kv_hi;
+            if constexpr (WIN) masked = masked || kvs < wave_q_last - a.window + 1;     // the last row's window edge
+            if (masked) {
 #pragma unroll
                 for (int s = 0; s < NSUB; ++s) {
                     const int qrow = row0[s] + li;
@@ -481,7 +497,8 @@ __global__ void __launch_bounds__(512) prefill_attn_kernel(PrefillArgs a) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const int kvi = kvs + t * 16 + 4 * g + r;
-                            const bool dead = kvi > qrow || kvi < ks_ || kvi >= kv_hi;
+                            bool dead = kvi > qrow || kvi < ks_ || kvi >= kv_hi;
+                            if constexpr (WIN) dead = dead || kvi < qrow - a.window + 1;
                             sc[s][t][r] = dead ? -INFINITY : sc[s][t][r];
                         }
                 }
@@ -551,10 +568,14 @@ extern "C" void slime_prefill_set_debug(void* counters) { g_prefill_dbg = (unsig
 static constexpr int g_prefill_variant = 0;
 #endif
 
-extern "C" int slime_prefill_attention(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v,
-                                       long v_bs, long v_rs, void* o, long o_bs, long o_rs, int batch, int n_heads,
-                                       int n_kv_heads, int head_dim, int S, const int32_t* kv_start, const int32_t* kv_len,
-                                       int dtype, void* stream) {
+// One implementation behind slime_prefill_attention (window 0) and slime_prefill_attention_window.  window == 0 or >= S: the
+// unwindowed kernels, the very launches of the existing entry.  0 < window < S: the WIN instantiation of the kernel the unwindowed
+// call would take -- prefill32_kernel for group 4 / bf16, the eight-wave kernel otherwise (and for diagnostic variant 1).
+static int prefill_attention_run(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v,
+                                 long v_bs, long v_rs, void* o, long o_bs, long o_rs, int batch, int n_heads,
+                                 int n_kv_heads, int head_dim, int S, const int32_t* kv_start, const int32_t* kv_len,
+                                 int dtype, int window, void* stream) {
+    SLIME_REQUIRE(window >= 0, "prefill_attention: window %d is negative (0: no window)", window);
     SLIME_REQUIRE(q && k && v && o, "prefill_attention: null pointer");
     SLIME_REQUIRE(batch > 0 && batch <= 65535 && S > 0, "prefill_attention: empty shape");
     SLIME_REQUIRE(head_dim == 128, "prefill_attention: head_dim %d unsupported (128)", head_dim);
@@ -566,11 +587,13 @@ extern "C" int slime_prefill_attention(const void* q, long q_bs, long q_rs, cons
     SLIME_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16 == 0, "prefill_attention: pointers must be 16-byte aligned");
     SLIME_REQUIRE((kv_start == nullptr) == (kv_len == nullptr), "prefill_attention: kv_start and kv_len come together");
     PrefillArgs a{(const char*)q, q_bs, q_rs, (const char*)k, k_bs, k_rs, (const char*)v, v_bs, v_rs, (char*)o, o_bs, o_rs,
-                  kv_start, kv_len, S, group, n_kv_heads, batch};
+                  kv_start, kv_len, S, group, n_kv_heads, batch, 0};
 #ifdef SLIME_DIAG
     a.dbg = g_prefill_dbg;
 #endif
     hipStream_t s = (hipStream_t)stream;
+    const bool win = window > 0 && window < S;                   // a window of S keys or more hides nothing: the causal kernels
+    if (win) a.window = window;
     if (group == 4 && dtype == SLIME_BF16 && g_prefill_variant != 1) {
         // Llama-3 geometry: one wave per SIMD, 32x32x16 MFMAs, K/V ring by LDS-DMA (prefill32.inc)
         // (persistent over its work items: one workgroup per CU -- the 128 KiB ring allows no second one -- walks the items in
@@ -581,7 +604,7 @@ extern "C" int slime_prefill_attention(const void* q, long q_bs, long q_rs, cons
         const int cus = num_cus() >= 8 ? (num_cus() & ~7) : 8;      // (a multiple of 8: the snake's mirror stays inside an XCD class)
         const int grid = (g_prefill_variant == 2 || items <= cus) ? (int)items : cus;
 #ifdef SLIME_DIAG
-        if (g_prefill_variant == 3) {                            // look-ahead of 4 key steps instead of 6
+        if (g_prefill_variant == 3 && !win) {                    // look-ahead of 4 key steps instead of 6 (unwindowed calls only)
             auto kern4 = prefill32_kernel<BF16, 4>;
             SLIME_SET_LDS_ONCE(kern4, LDS32, "prefill_attention");
             hipLaunchKernelGGL(kern4, dim3(grid), dim3(256), LDS32, s, a);
@@ -589,16 +612,30 @@ extern "C" int slime_prefill_attention(const void* q, long q_bs, long q_rs, cons
             return SLIME_OK;
         }
 #endif
-        auto kern = prefill32_kernel<BF16>;
-        SLIME_SET_LDS_ONCE(kern, LDS32, "prefill_attention");
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDS32, s, a);
+        if (win) {
+            auto kern = prefill32_kernel<BF16, 6, true>;
+            SLIME_SET_LDS_ONCE(kern, LDS32, "prefill_attention");
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDS32, s, a);
+        } else {
+            auto kern = prefill32_kernel<BF16>;
+            SLIME_SET_LDS_ONCE(kern, LDS32, "prefill_attention");
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDS32, s, a);
+        }
         SLIME_CHECK_LAUNCH("prefill_attention");
         return SLIME_OK;
     }
     constexpr int LDS = 2 * 192 * 256;
     const int QB = 256 / group, nqb = (S + QB - 1) / QB;
     SLIME_REQUIRE(nqb <= 65535, "prefill_attention: sequence too long");
-    if (dtype == SLIME_F16) {
+    if (win && dtype == SLIME_F16) {
+        auto kern = prefill_attn_kernel<F16, true>;
+        SLIME_SET_LDS_ONCE(kern, LDS, "prefill_attention");
+        hipLaunchKernelGGL(kern, dim3(n_kv_heads, batch, nqb), dim3(512), LDS, s, a);
+    } else if (win && dtype == SLIME_BF16) {
+        auto kern = prefill_attn_kernel<BF16, true>;
+        SLIME_SET_LDS_ONCE(kern, LDS, "prefill_attention");
+        hipLaunchKernelGGL(kern, dim3(n_kv_heads, batch, nqb), dim3(512), LDS, s, a);
+    } else if (dtype == SLIME_F16) {
         auto kern = prefill_attn_kernel<F16>;
         SLIME_SET_LDS_ONCE(kern, LDS, "prefill_attention");
         hipLaunchKernelGGL(kern, dim3(n_kv_heads, batch, nqb), dim3(512), LDS, s, a);
@@ -612,6 +649,22 @@ extern "C" int slime_prefill_attention(const void* q, long q_bs, long q_rs, cons
     }
     SLIME_CHECK_LAUNCH("prefill_attention");
     return SLIME_OK;
+}
+
+extern "C" int slime_prefill_attention(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v,
+                                       long v_bs, long v_rs, void* o, long o_bs, long o_rs, int batch, int n_heads,
+                                       int n_kv_heads, int head_dim, int S, const int32_t* kv_start, const int32_t* kv_len,
+                                       int dtype, void* stream) {
+    return prefill_attention_run(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, o, o_bs, o_rs, batch, n_heads, n_kv_heads, head_dim, S,
+                                 kv_start, kv_len, dtype, 0, stream);
+}
+
+extern "C" int slime_prefill_attention_window(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v,
+                                              long v_bs, long v_rs, void* o, long o_bs, long o_rs, int batch, int n_heads,
+                                              int n_kv_heads, int head_dim, int S, const int32_t* kv_start, const int32_t* kv_len,
+                                              int dtype, int window, void* stream) {
+    return prefill_attention_run(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, o, o_bs, o_rs, batch, n_heads, n_kv_heads, head_dim, S,
+                                 kv_start, kv_len, dtype, window, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ LlamaAttention.forward
@@ -632,12 +685,13 @@ extern "C" size_t slime_llama_attn_workspace_bytes(const slime_llama_attn_desc* 
     return qkv + ctx;
 }
 
-// One implementation behind both entry points: resid == NULL -> out = o_proj(ctx) (T or fp32); else out = T(resid + o_proj(ctx)).
+// One implementation behind the three entry points: resid == NULL -> out = o_proj(ctx) (T or fp32); else out = T(resid + o_proj(ctx)).
 static int llama_attn_run(const slime_llama_attn_desc* d, const void* hidden, const int32_t* position_ids, const int32_t* kv_start,
                           const int32_t* kv_len, int batch, int S, void* out, int out_dtype, const void* resid,
-                          void* ws, size_t ws_bytes, void* stream) {
+                          void* ws, size_t ws_bytes, void* stream, int window) {
     int rc = llama_validate(d);
     if (rc != SLIME_OK) return rc;
+    SLIME_REQUIRE(window >= 0, "llama_attn: window %d is negative (0: no window)", window);     // before the first launch
     SLIME_REQUIRE(hidden && position_ids && out && batch > 0 && S > 0, "llama_attn: bad input");
     const size_t need = slime_llama_attn_workspace_bytes(d, batch, S);
     if (!ws || ws_bytes < need || ((uintptr_t)ws % 256) != 0) {
@@ -657,9 +711,9 @@ static int llama_attn_run(const slime_llama_attn_desc* d, const void* hidden, co
     // RoPE on q and k (:51-54); q also takes head_dim^-0.5 * log2(e)
     rc = slime_rope(qkv, NQKV, position_ids, M, HQ + HKV, HQ, DH, d->inv_freq, 0.08838834764831845f * 1.4426950408889634f, d->dtype, stream);
     if (rc != SLIME_OK) return rc;
-    rc = slime_prefill_attention(qkv, (long)S * NQKV, NQKV, qkv + (size_t)HQ * DH * 2, (long)S * NQKV, NQKV,
-                                 qkv + (size_t)(HQ + HKV) * DH * 2, (long)S * NQKV, NQKV, ctx, (long)S * HQ * DH, HQ * DH, batch,
-                                 HQ, HKV, DH, S, kv_start, kv_len, d->dtype, stream);
+    rc = prefill_attention_run(qkv, (long)S * NQKV, NQKV, qkv + (size_t)HQ * DH * 2, (long)S * NQKV, NQKV,
+                               qkv + (size_t)(HQ + HKV) * DH * 2, (long)S * NQKV, NQKV, ctx, (long)S * HQ * DH, HQ * DH, batch,
+                               HQ, HKV, DH, S, kv_start, kv_len, d->dtype, window, stream);
     if (rc != SLIME_OK) return rc;
     // o_proj (:92), optionally with the decoder layer's residual add in its epilogue
     ga = slime_gemm_args{};
@@ -675,7 +729,7 @@ extern "C" int slime_llama_attn_forward(const slime_llama_attn_desc* d, const vo
                                         void* ws, size_t ws_bytes, void* stream) {
     SLIME_REQUIRE(d && out, "llama_attn: bad input");
     SLIME_REQUIRE(out_dtype == d->dtype || out_dtype == SLIME_F32, "llama_attn: out dtype must be the operand type or F32");
-    return llama_attn_run(d, hidden, position_ids, kv_start, kv_len, batch, S, out, out_dtype, nullptr, ws, ws_bytes, stream);
+    return llama_attn_run(d, hidden, position_ids, kv_start, kv_len, batch, S, out, out_dtype, nullptr, ws, ws_bytes, stream, 0);
 }
 
 extern "C" int slime_llama_attn_forward_resid(const slime_llama_attn_desc* d, const void* hidden, const int32_t* position_ids,
@@ -683,5 +737,18 @@ extern "C" int slime_llama_attn_forward_resid(const slime_llama_attn_desc* d, co
                                               void* out, void* ws, size_t ws_bytes, void* stream) {
     SLIME_REQUIRE(d && resid && out, "llama_attn_resid: resid and out are required");
     SLIME_REQUIRE(hidden != out, "llama_attn_resid: out may alias resid, not the layer's input rows");
-    return llama_attn_run(d, hidden, position_ids, kv_start, kv_len, batch, S, out, d->dtype, resid, ws, ws_bytes, stream);
+    return llama_attn_run(d, hidden, position_ids, kv_start, kv_len, batch, S, out, d->dtype, resid, ws, ws_bytes, stream, 0);
+}
+
+extern "C" int slime_llama_attn_forward_window(const slime_llama_attn_desc* d, const void* hidden, const int32_t* position_ids,
+                                               const int32_t* kv_start, const int32_t* kv_len, int batch, int S, const void* resid,
+                                               void* out, int out_dtype, int window, void* ws, size_t ws_bytes, void* stream) {
+    SLIME_REQUIRE(d && out, "llama_attn: bad input");
+    if (resid) {
+        SLIME_REQUIRE(out_dtype == d->dtype, "llama_attn_resid: out dtype must be the operand type");
+        SLIME_REQUIRE(hidden != out, "llama_attn_resid: out may alias resid, not the layer's input rows");
+    } else {
+        SLIME_REQUIRE(out_dtype == d->dtype || out_dtype == SLIME_F32, "llama_attn: out dtype must be the operand type or F32");
+    }
+    return llama_attn_run(d, hidden, position_ids, kv_start, kv_len, batch, S, out, out_dtype, resid, ws, ws_bytes, stream, window);
 }

@@ -38,7 +38,16 @@
 // fullest workgroup against 95 on average, 5 items against 4).  "Three 32-row blocks per wave" (VERDICT r2) does not fit: the
 // two blocks already hold 160 AGPRs + 256 VGPRs (64 of them Q); a third needs 80 + 32 more.
 
-template <typename T, int P = 6>                               // P: key steps requested ahead of their use (6; 4 = measured alternative)
+// WIN: the sliding-window instantiation (Mistral / Mixtral: query row i sees key j iff j <= i and i - j < a.window).  An item's first
+// step becomes max(ks, q_lo - W + 1) >> 5 -- generator, ring bookkeeping and consumer all take their step counts from load_item, so
+// they agree by construction and behind the window every item is ceil((W + 63 + 31) / 32)-ish steps long.  The leading steps up to
+// and including the one that holds the LAST row's first visible key, q_lo + 64 - W (32 st <= q_lo + 64 - W: up to three behind
+// t_first), get a two-sided mask with a per-row lower bound.  The test is inclusive: q_lo is a multiple of 64, so for every W
+// that is a multiple of 32 (4096, the Mistral default) that key is the FIRST key of its step, and the last row starts there.  A row whose window opens in such a step has seen no live key yet: take_reference left its reference at 0 and its
+// accumulators are exact zeros, so the step it STARTS in sets the reference to its row maximum whatever the sign (the lazy rescale
+// alone only ever moves up, and scores far below 0 would underflow P) and leaves the zero accumulators alone (alpha = 1: 0 x inf
+// would be NaN).  Every row starts in t_first or in one of those leading steps.  WIN = false compiles the code as it was.
+template <typename T, int P = 6, bool WIN = false>             // P: key steps requested ahead of their use (6; 4 = measured alternative)
 __global__ void __launch_bounds__(256) prefill32_kernel(PrefillArgs a) {
     static_assert(P == 4 || P == 6, "the pair loop needs an even look-ahead of at least 4 steps inside the 8-slot ring");
     constexpr int RB = 256, NB = 2, R = 8, STEP = 32 * RB, GROUP = 4;
@@ -68,6 +77,7 @@ __global__ void __launch_bounds__(256) prefill32_kernel(PrefillArgs a) {
         it.ke = a.kv_len ? min(a.S, it.ks + a.kv_len[it.b]) : a.S;
         const int kv_hi = min(it.ke, it.q_lo + 64);                // causal: no key beyond the last query row
         it.t_first = it.ks >> 5;
+        if constexpr (WIN) it.t_first = max(it.ks, it.q_lo - a.window + 1) >> 5;
         it.t_end = (kv_hi + 31) >> 5;
         if (it.t_end <= it.t_first || it.q_lo >= it.ke) it.t_end = it.t_first;    // no query row inside the token range
         return true;
@@ -217,8 +227,11 @@ __global__ void __launch_bounds__(256) prefill32_kernel(PrefillArgs a) {
         int d = lim[blk] - (step * 32 + 4 * hh);
         asm volatile("" : "+v"(d));                           // opaque: hipcc otherwise hoists the compares of a mask into the
                                                               // unmasked path of every iteration
-        if (__builtin_expect(ks_ > step * 32, 0)) {
-            const int lo = ks_ - (step * 32 + 4 * hh);
+        bool two_sided = ks_ > step * 32;
+        if constexpr (WIN) two_sided = two_sided || step * 32 <= q_lo + 64 - a.window;       // (uniform: the item's last row's edge)
+        if (__builtin_expect(two_sided, 0)) {
+            int lo = ks_ - (step * 32 + 4 * hh);
+            if constexpr (WIN) lo = max(ks_, lim[blk] - a.window + 1) - (step * 32 + 4 * hh); // per row (lim = -1: d < 0, all dead)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int off = (r & 3) + 8 * (r >> 2);
@@ -262,7 +275,9 @@ __global__ void __launch_bounds__(256) prefill32_kernel(PrefillArgs a) {
 
     // ---- one step = two iterations of the pipeline ----
     auto step = [&](const int st) __attribute__((always_inline)) {                            // its second iteration requests one more step of the ring
-        const bool masked = st == t_first || st >= t_diag;
+        bool masked = st == t_first || st >= t_diag;
+        bool win_lead = false;                                 // a leading step behind t_first in which rows may start (WIN only)
+        if constexpr (WIN) { win_lead = st > t_first && st * 32 <= q_lo + 64 - a.window; masked = masked || win_lead; }
 #pragma unroll
         for (int s = 0; s < NB; ++s)                          // (the accumulators stay in the AGPR file across every edge of the loop nest)
             asm volatile("" : "+a"(o[s][0]), "+a"(o[s][1]), "+a"(o[s][2]), "+a"(o[s][3]), "+a"(osum[s]));
@@ -321,7 +336,7 @@ __global__ void __launch_bounds__(256) prefill32_kernel(PrefillArgs a) {
                 asm volatile(A32_MFB : [accb] "+a"(av) : [mab] "v"(mab), [mbb] "v"(mbb));
             }
             if (!last) { v_request1(); k_advance(); }
-            if (__builtin_expect(runaway != 0, 0)) {
+            if (__builtin_expect(runaway != 0 || win_lead, 0)) {
                 float mx = sc[0];
 #pragma unroll
                 for (int r = 1; r < 16; ++r) mx = __builtin_fmaxf(mx, sc[r]);
@@ -330,13 +345,18 @@ __global__ void __launch_bounds__(256) prefill32_kernel(PrefillArgs a) {
                 // only the rows that ran away themselves move (a row's result must not depend on what shares its block: changing
                 // LATER tokens may not change earlier rows by a bit); for the others d = 0 reproduces the speculative values
                 float d = __builtin_fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-                d = d > RESCALE_TH ? d : 0.f;
+                bool starting = false;
+                if constexpr (WIN) {                           // this row's first live key lies in this step: its reference is this maximum
+                    const int first_key = max(ks_, lim[blk] - a.window + 1);
+                    starting = win_lead && lim[blk] >= 0 && first_key >= st * 32 && first_key < st * 32 + 32;
+                }
+                d = (d > RESCALE_TH || starting) ? d : 0.f;
                 m_ref[blk] += d;
                 set_reference(qx[blk], m_ref[blk]);
 #pragma unroll
                 for (int q = 0; q < 8; ++q)
                     pk[q] = T::pack2(__builtin_amdgcn_exp2f(sc[2 * q] - d), __builtin_amdgcn_exp2f(sc[2 * q + 1] - d));
-                const float alpha = __builtin_amdgcn_exp2f(-d);
+                const float alpha = starting ? 1.0f : __builtin_amdgcn_exp2f(-d);     // (a starting row's accumulators are zeros)
                 asm volatile("s_nop 7\n\ts_nop 7" : "+a"(o[blk][0]), "+a"(o[blk][1]), "+a"(o[blk][2]), "+a"(o[blk][3]), "+a"(osum[blk]));
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {

@@ -1740,43 +1740,83 @@ def _position_ids(position_ids: Optional[torch.Tensor], B: int, S: int, device) 
     return pos
 
 
+def _llama_attention(pa: PackedLlamaAttention, hidden: torch.Tensor, position_ids, attention_mask, out_dtype, resid, out,
+                     window: Optional[int]) -> torch.Tensor:
+    """The one host sequence behind ``llama_attention_forward`` / ``_resid`` / ``_window``: operands, position ids, token ranges,
+    output and workspace, then ONE C-ABI call -- ``window`` None: slime_llama_attn_forward or, with ``resid``, _forward_resid (the
+    launches those two functions always made); an int: slime_llama_attn_forward_window."""
+    lib = _lib.load()
+    _require_cuda(hidden, "hidden")
+    B, S, D = hidden.shape
+    assert D == pa.hidden
+    if resid is not None:
+        assert hidden.dtype == pa.dtype and resid.dtype == pa.dtype and tuple(resid.shape) == (B, S, D) and out_dtype in (None, pa.dtype)
+        x, r = hidden.contiguous(), resid.contiguous()
+        out_dtype = kernel_out = pa.dtype
+    else:
+        x, r = hidden.to(pa.dtype).contiguous(), None
+        out_dtype = out_dtype or hidden.dtype
+        kernel_out = torch.float32 if out_dtype == torch.float32 else pa.dtype
+    pos = _position_ids(position_ids, B, S, x.device)
+    start, length = token_ranges(None if attention_mask is None else attention_mask.to(x.device))
+    if out is None:
+        out = torch.empty((B, S, D), dtype=kernel_out, device=x.device)
+    assert out.is_contiguous() and out.dtype == kernel_out and tuple(out.shape) == (B, S, D) and out.data_ptr() != x.data_ptr()
+    need = lib.slime_llama_attn_workspace_bytes(C.byref(pa.desc), B, S)
+    base, avail = pa.ws.aligned(need, x.device)
+    head = (C.byref(pa.desc), x.data_ptr(), pos.data_ptr(), _ptr(start), _ptr(length), B, S)
+    if window is not None:
+        _lib.check(lib.slime_llama_attn_forward_window(*head, None if r is None else r.data_ptr(), out.data_ptr(), dtype_code(kernel_out),
+                                                       int(window), base, avail, _stream()), "slime_llama_attn_forward_window")
+    elif r is not None:
+        _lib.check(lib.slime_llama_attn_forward_resid(*head, r.data_ptr(), out.data_ptr(), base, avail, _stream()),
+                   "slime_llama_attn_forward_resid")
+    else:
+        _lib.check(lib.slime_llama_attn_forward(*head, out.data_ptr(), dtype_code(kernel_out), base, avail, _stream()),
+                   "slime_llama_attn_forward")
+    return out if out.dtype == out_dtype else out.to(out_dtype)
+
+
 def llama_attention_forward_resid(pa: PackedLlamaAttention, hidden: torch.Tensor, resid: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
                                   attention_mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The attention sub-layer with the decoder layer's residual add in o_proj's epilogue (slime_llama_attn_forward_resid):
     out = T(resid + self_attn(hidden)), all T [B, S, D].  ``out`` may be ``resid`` itself (in-place stream); ``hidden`` may be
     ``resid`` (no norm in between) but not ``out``."""
-    lib = _lib.load()
-    _require_cuda(hidden, "hidden")
-    B, S, D = hidden.shape
-    assert D == pa.hidden and hidden.dtype == pa.dtype and resid.dtype == pa.dtype and tuple(resid.shape) == (B, S, D)
-    x, r = hidden.contiguous(), resid.contiguous()
-    pos = _position_ids(position_ids, B, S, x.device)
-    start, length = token_ranges(None if attention_mask is None else attention_mask.to(x.device))
-    if out is None:
-        out = torch.empty((B, S, D), dtype=pa.dtype, device=x.device)
-    assert out.is_contiguous() and out.dtype == pa.dtype and out.data_ptr() != x.data_ptr()
-    need = lib.slime_llama_attn_workspace_bytes(C.byref(pa.desc), B, S)
-    base, avail = pa.ws.aligned(need, x.device)
-    _lib.check(lib.slime_llama_attn_forward_resid(C.byref(pa.desc), x.data_ptr(), pos.data_ptr(), _ptr(start), _ptr(length), B, S,
-                                                  r.data_ptr(), out.data_ptr(), base, avail, _stream()), "slime_llama_attn_forward_resid")
-    return out
+    return _llama_attention(pa, hidden, position_ids, attention_mask, None, resid, out, None)
 
 
 def llama_attention_forward(pa: PackedLlamaAttention, hidden: torch.Tensor, position_ids: Optional[torch.Tensor] = None,
                             attention_mask: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """hidden [B, S, D] -> [B, S, D]: q/k/v projection, RoPE, causal GQA attention over the un-padded tokens, o_proj."""
+    return _llama_attention(pa, hidden, position_ids, attention_mask, out_dtype, None, None, None)
+
+
+def llama_attention_forward_window(pa: PackedLlamaAttention, hidden: torch.Tensor, position_ids: Optional[torch.Tensor],
+                                   attention_mask: Optional[torch.Tensor], out_dtype: Optional[torch.dtype], window: int,
+                                   resid: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The attention sub-layer with a sliding window (slime_llama_attn_forward_window; MistralAttention / MixtralAttention):
+    query row i sees key row j iff j <= i, i - j < window and both lie in the sequence's token run; ``window`` 0 (or >= S) is
+    ``llama_attention_forward`` / ``_resid`` bit for bit, a negative one is refused by the library.  ``resid`` given:
+    out = T(resid + self_attn(hidden)) (``out`` may be ``resid``); else [B, S, D] of ``out_dtype`` (default: hidden's)."""
+    return _llama_attention(pa, hidden, position_ids, attention_mask, out_dtype, resid, out, int(window))
+
+
+def prefill_attention_window(qkv: torch.Tensor, n_heads: int, n_kv_heads: int, window: int,
+                             attention_mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Sliding-window causal GQA attention (slime_prefill_attention_window) on a packed [B, S, (n_heads + 2 n_kv_heads) * 128]
+    buffer of q | k | v heads -- q pre-scaled by 128^-0.5 log2 e, RoPE applied, as ``slime_rope`` leaves it -> [B, S, n_heads * 128].
+    ``window`` as in ``llama_attention_forward_window``."""
     lib = _lib.load()
-    _require_cuda(hidden, "hidden")
-    B, S, D = hidden.shape
-    assert D == pa.hidden
-    x = hidden.to(pa.dtype).contiguous()
-    pos = _position_ids(position_ids, B, S, x.device)
-    start, length = token_ranges(None if attention_mask is None else attention_mask.to(x.device))
-    out_dtype = out_dtype or hidden.dtype
-    kernel_out = torch.float32 if out_dtype == torch.float32 else pa.dtype
-    out = torch.empty((B, S, D), dtype=kernel_out, device=x.device)
-    need = lib.slime_llama_attn_workspace_bytes(C.byref(pa.desc), B, S)
-    base, avail = pa.ws.aligned(need, x.device)
-    _lib.check(lib.slime_llama_attn_forward(C.byref(pa.desc), x.data_ptr(), pos.data_ptr(), _ptr(start), _ptr(length), B, S,
-                                            out.data_ptr(), dtype_code(kernel_out), base, avail, _stream()), "slime_llama_attn_forward")
-    return out if out.dtype == out_dtype else out.to(out_dtype)
+    _require_cuda(qkv, "qkv")
+    B, S, N = qkv.shape
+    assert qkv.is_contiguous() and qkv.dtype in (torch.bfloat16, torch.float16) and N == (n_heads + 2 * n_kv_heads) * 128
+    start, length = token_ranges(None if attention_mask is None else attention_mask.to(qkv.device))
+    if out is None:
+        out = torch.empty((B, S, n_heads * 128), dtype=qkv.dtype, device=qkv.device)
+    assert out.is_contiguous() and out.dtype == qkv.dtype and tuple(out.shape) == (B, S, n_heads * 128)
+    p = qkv.data_ptr()
+    _lib.check(lib.slime_prefill_attention_window(p, S * N, N, p + n_heads * 256, S * N, N, p + (n_heads + n_kv_heads) * 256, S * N, N,
+                                                  out.data_ptr(), S * n_heads * 128, n_heads * 128, B, n_heads, n_kv_heads, 128, S,
+                                                  _ptr(start), _ptr(length), dtype_code(qkv.dtype), int(window), _stream()),
+               "slime_prefill_attention_window")
+    return out
