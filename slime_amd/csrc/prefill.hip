@@ -1,16 +1,19 @@
 // prefill.hip -- the step after the visual hot path (BASELINE configs 4 / 5): splicing the visual
 // tokens into the text embeddings and the Llama-3 prefill self-attention over the spliced sequence.
 //
-//   slime_splice_rows        new_input_embeds of prepare_inputs_labels_for_multimodal (llava/model/llava_arch.py:343-459): every
-//                            output row is a row of the embedding table, a row of the image features, or zero padding.  The
-//                            index plan is integer host logic (slime_amd/model/llava_arch.py); ALL tensor movement -- what the
-//                            reference does with per-sequence torch.cat / split / stack calls -- is this one launch.
-//   slime_splice_routed      the same rows without the per-image feature tensors in between: an image row names (image, position) and
-//                            is resolved on the device from the batched router's arrays and the fp32 token buffer (opt-in:
-//                            cfg.fused_splice), with the two roundings of the per-image path -- the same bits.
-//   slime_splice_merged      the same rows for the un-sampled LLaVA-NeXT merge ('spatial' / 'spatial_unpad'): an image row names a row
-//                            of the projector's fp32 output (or the image_newline row) directly, the merged per-image features are
-//                            never built; same two roundings, same bits.
+//   slime_splice_rows / slime_splice_routed / slime_splice_merged
+//                            new_input_embeds of prepare_inputs_labels_for_multimodal (llava/model/llava_arch.py:343-459): every
+//                            output row is a row of the embedding table, an image row, or zero padding.  The index plan is
+//                            integer host logic (slime_amd/model/llava_arch.py); ALL tensor movement -- what the reference does
+//                            with per-sequence torch.cat / split / stack calls -- is one launch, one wave per output row.  The
+//                            three are one kernel shape: each resolves its own encoding of `src` to a source row, ONE body writes
+//                            the row.  They differ in what an image row names:
+//                              _rows    a row of the per-image feature tensors;
+//                              _routed  (image, position), resolved on the device from the batched router's arrays and the fp32
+//                                       token buffer (opt-in: cfg.fused_splice) -- no per-image feature tensors in between;
+//                              _merged  a row of the projector's fp32 output or the image_newline row (the un-sampled LLaVA-NeXT
+//                                       merge, 'spatial' / 'spatial_unpad') -- the merged per-image features are never built.
+//                            _routed and _merged give an fp32 row the two roundings of the per-image path: the same bits.
 //   slime_rope               RoPE on the q and k heads of a packed qkv buffer, in place (HF rotate_half convention: pairs
 //                            (i, i + d/2); fp32 cos/sin of pos * inv_freq), q additionally scaled by head_dim^-0.5 * log2 e
 //                            (the attention kernels work in log2 units).
@@ -31,6 +34,14 @@
 #include "common.h"
 
 // ------------------------------------------------------------------------------------------------ splice
+// Three kernels of one shape, one wave per output row: r = the wave's row, src[r] is RESOLVED to a SpliceRow (the three differ in
+// this step only: splice_resolve_rows / _routed / _merged carry the encodings of `src`), splice_emit writes the row.  In all three
+// src >= 0 is a row of the embedding table, src == -1 a zero row and src <= -2 an image row; a source that resolves outside its
+// tensor is never dereferenced: the row is zeroed (the host plans raise on such ids first, as nn.Embedding does; this is the
+// device-side backstop for direct C-ABI callers).  The routed and merged resolvers assign to defaulted variables and return once:
+// written with early returns they compile to one more dependent round of kernel-argument loads per wave in front of the row's first
+// load, which a wave that lives for one row does not hide (measured on slime_splice_merged: +0.4 %).
+
 __device__ __forceinline__ float load_as_float(const void* p, int dtype, size_t i) {
     if (dtype == SLIME_F32) return reinterpret_cast<const float*>(p)[i];
     const unsigned short h = reinterpret_cast<const unsigned short*>(p)[i];
@@ -42,52 +53,6 @@ __device__ __forceinline__ void store_from_float(void* p, int dtype, size_t i, f
     else if (dtype == SLIME_BF16) reinterpret_cast<unsigned short*>(p)[i] = (unsigned short)(BF16::pack2(v, 0.f) & 0xffffu);
     else reinterpret_cast<unsigned short*>(p)[i] = (unsigned short)(F16::pack2(v, 0.f) & 0xffffu);
 }
-
-// One wave per output row.  src >= 0: row src of `table`; src <= -2: row (-2 - src) of `feats`; src == -1: zeros.
-// Equal source / destination dtypes are copied bit for bit (16 B per lane per step when the row allows).
-__global__ void __launch_bounds__(256) splice_rows_kernel(const void* table, int table_dtype, const void* feats, int feats_dtype,
-                                                          const long long* src, void* out, int out_dtype, long rows, int H,
-                                                          long table_rows, long feat_rows) {
-    const int lane = threadIdx.x & 63;
-    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;
-    const long long s = src[r];
-    const int es_out = out_dtype == SLIME_F32 ? 4 : 2;
-    char* o = reinterpret_cast<char*>(out) + (size_t)r * H * es_out;
-    // a source row outside its tensor is never dereferenced: the row is zeroed (the host plan raises on such ids first, as
-    // nn.Embedding does; this is the device-side backstop for direct C-ABI callers)
-    if (s == -1 || (s >= 0 && s >= table_rows) || (s <= -2 && -2 - s >= feat_rows)) {
-        for (int b = lane * 16; b < H * es_out; b += 1024) *reinterpret_cast<u32x4*>(o + b) = u32x4{0u, 0u, 0u, 0u};
-        return;
-    }
-    const void* base = s >= 0 ? table : feats;
-    const int dt = s >= 0 ? table_dtype : feats_dtype;
-    const size_t row = s >= 0 ? (size_t)s : (size_t)(-2 - s);
-    if (dt == out_dtype) {
-        const char* p = reinterpret_cast<const char*>(base) + row * (size_t)H * es_out;
-        for (int b = lane * 16; b < H * es_out; b += 1024) *reinterpret_cast<u32x4*>(o + b) = *reinterpret_cast<const u32x4*>(p + b);
-        return;
-    }
-    for (int c = lane; c < H; c += 64) store_from_float(out, out_dtype, (size_t)r * H + c, load_as_float(base, dt, row * (size_t)H + c));
-}
-
-extern "C" int slime_splice_rows(const void* table, int table_dtype, long table_rows, const void* feats, int feats_dtype,
-                                 long feat_rows, const int64_t* src, void* out, int out_dtype, long rows, int H, void* stream) {
-    SLIME_REQUIRE(src && out && rows > 0 && H > 0, "splice_rows: bad input");
-    SLIME_REQUIRE(table || feats, "splice_rows: neither an embedding table nor image features");
-    SLIME_REQUIRE(table_rows >= 0 && feat_rows >= 0, "splice_rows: negative source size");
-    auto ok = [](int dt) { return dt == SLIME_F32 || dt == SLIME_BF16 || dt == SLIME_F16; };
-    SLIME_REQUIRE(ok(out_dtype) && (!table || ok(table_dtype)) && (!feats || ok(feats_dtype)), "splice_rows: bad dtype");
-    SLIME_REQUIRE((H * (out_dtype == SLIME_F32 ? 4 : 2)) % 16 == 0, "splice_rows: rows must be multiples of 16 bytes (H=%d)", H);
-    SLIME_REQUIRE(((uintptr_t)out % 16) == 0 && ((uintptr_t)table % 16) == 0 && ((uintptr_t)feats % 16) == 0, "splice_rows: pointers must be 16-byte aligned");
-    hipLaunchKernelGGL(splice_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, table, table_dtype,
-                       feats, feats_dtype, reinterpret_cast<const long long*>(src), out, out_dtype, rows, H,
-                       table ? table_rows : 0, feats ? feat_rows : 0);
-    SLIME_CHECK_LAUNCH("splice_rows");
-    return SLIME_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ routed splice
 // fp32 -> dtype -> fp32: the rounding a tensor.to(dtype) leaves in the value (SLIME_F32: none).
 __device__ __forceinline__ float round_through(float v, int dtype) {
     if (dtype == SLIME_BF16) return BF16::lo(BF16::pack2(v, 0.f));
@@ -98,23 +63,89 @@ __device__ __forceinline__ unsigned pack2_as(float lo, float hi, int dtype) {
     return dtype == SLIME_BF16 ? BF16::pack2(lo, hi) : F16::pack2(lo, hi);
 }
 
-// One wave per output row, as splice_rows_kernel, but the image-feature rows [glob | sep | routed] are never materialised: the row's
-// source is resolved from the router's device arrays (wave-uniform loads), and an fp32 token row goes to the output through the
-// two roundings of today's tokens.to(images.dtype) -> splice cast, 16 B per lane in, 16 B per lane out.
-//   src >= 0: table row (splice_rows' rule); src == -1: zeros; src <= -2: q = -2 - src, image b = q >> 32, position p = q & 0xffffffff:
-//   p < P global token row local_row_off[b] - P + p; p == P table row sep_id; p > P token row local_row_off[b] + keep_idx[b, p - P - 1].
-// A source that resolves outside its tensor is never dereferenced: the row is zeroed.
-__global__ void __launch_bounds__(256) splice_routed_kernel(const void* table, int table_dtype, long table_rows, long sep_id,
-                                                            const float* tokens, long token_rows, const long long* local_row_off,
-                                                            const int* n_rows, int B, int P, int T_max, const int* keep_idx,
-                                                            const int* keep_count, int mid_dtype, const long long* src, void* out,
-                                                            int out_dtype, long rows, int H) {
+// What an output row is made of.
+struct SpliceRow {
+    enum Kind { ZERO, TYPED, TOKEN } kind;      // zeros | row `row` of a tensor of `dtype` | row `row` of the fp32 token buffer
+    const void* base;
+    int dtype;
+    size_t row;
+    bool via_mid;                               // TYPED: the value takes tensor.to(mid_dtype) first, as every TOKEN row does: two roundings
+    static __device__ __forceinline__ SpliceRow zero() { return {ZERO, nullptr, SLIME_F32, 0, false}; }
+    static __device__ __forceinline__ SpliceRow typed(const void* base, int dtype, long long row, bool via_mid = false) {
+        return {TYPED, base, dtype, (size_t)row, via_mid};
+    }
+    static __device__ __forceinline__ SpliceRow token(const float* tokens, long long row) { return {TOKEN, tokens, SLIME_F32, (size_t)row, true}; }
+};
+
+// The wave's output row: wave-uniform, so src[r] and everything resolved from it are scalar loads.
+__device__ __forceinline__ long splice_wave_row() { return (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+
+// Writes output row r.  Rows of the output's own type are copied bit for bit; a token row goes fp32 -> mid -> out with 16 B per
+// lane in and out; every other row is cast element by element.  All row offsets are 64-bit.
+__device__ __forceinline__ void splice_emit(const SpliceRow s, int mid_dtype, void* out, int out_dtype, size_t r, int H) {
     const int lane = threadIdx.x & 63;
-    const long r = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (r >= rows) return;
-    const long long s = src[r];
     const int es_out = out_dtype == SLIME_F32 ? 4 : 2;
-    char* o = reinterpret_cast<char*>(out) + (size_t)r * H * es_out;
+    char* o = reinterpret_cast<char*>(out) + r * H * es_out;
+    if (s.kind == SpliceRow::ZERO) {
+        for (int b = lane * 16; b < H * es_out; b += 1024) *reinterpret_cast<u32x4*>(o + b) = u32x4{0u, 0u, 0u, 0u};
+        return;
+    }
+    if (s.kind == SpliceRow::TOKEN) {                     // always through mid_dtype
+        const int mid = mid_dtype;
+        const float* t = reinterpret_cast<const float*>(s.base) + s.row * H;
+        if (out_dtype == SLIME_F32) {
+            for (int c = lane * 4; c < H; c += 256) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(t + c);
+                *reinterpret_cast<f32x4*>(o + (size_t)c * 4) = f32x4{round_through(v[0], mid), round_through(v[1], mid),
+                                                                      round_through(v[2], mid), round_through(v[3], mid)};
+            }
+            return;
+        }
+        for (int c = lane * 8; c < H; c += 512) {         // a 16-bit output row of whole 16-byte pieces: H is a multiple of 8
+            const f32x4 v0 = *reinterpret_cast<const f32x4*>(t + c), v1 = *reinterpret_cast<const f32x4*>(t + c + 4);
+            u32x4 w;
+            w[0] = pack2_as(round_through(v0[0], mid), round_through(v0[1], mid), out_dtype);
+            w[1] = pack2_as(round_through(v0[2], mid), round_through(v0[3], mid), out_dtype);
+            w[2] = pack2_as(round_through(v1[0], mid), round_through(v1[1], mid), out_dtype);
+            w[3] = pack2_as(round_through(v1[2], mid), round_through(v1[3], mid), out_dtype);
+            *reinterpret_cast<u32x4*>(o + (size_t)c * 2) = w;
+        }
+        return;
+    }
+    if (!s.via_mid && s.dtype == out_dtype) {
+        const char* p = reinterpret_cast<const char*>(s.base) + s.row * H * es_out;
+        for (int b = lane * 16; b < H * es_out; b += 1024) *reinterpret_cast<u32x4*>(o + b) = *reinterpret_cast<const u32x4*>(p + b);
+        return;
+    }
+    const int mid = s.via_mid ? mid_dtype : SLIME_F32;
+    for (int c = lane; c < H; c += 64)
+        store_from_float(out, out_dtype, r * H + c, round_through(load_as_float(s.base, s.dtype, s.row * H + c), mid));
+}
+
+// slime_splice_rows.  src >= 0: row src of `table`; src <= -2: row (-2 - src) of `feats`, which is cast once, with no middle
+// rounding (an fp32 `feats` row too: it stays on the element-wise cast); src == -1: zeros.
+__device__ __forceinline__ SpliceRow splice_resolve_rows(long long s, const void* table, int table_dtype, long table_rows,
+                                                         const void* feats, int feats_dtype, long feat_rows) {
+    if (s >= 0 && s < table_rows) return SpliceRow::typed(table, table_dtype, s);
+    if (s <= -2 && -2 - s < feat_rows) return SpliceRow::typed(feats, feats_dtype, -2 - s);
+    return SpliceRow::zero();
+}
+__global__ void __launch_bounds__(256) splice_rows_kernel(const void* table, int table_dtype, const void* feats, int feats_dtype,
+                                                          const long long* src, void* out, int out_dtype, long rows, int H,
+                                                          long table_rows, long feat_rows) {
+    const long r = splice_wave_row();
+    if (r >= rows) return;
+    splice_emit(splice_resolve_rows(src[r], table, table_dtype, table_rows, feats, feats_dtype, feat_rows), SLIME_F32, out, out_dtype, r, H);
+}
+
+// slime_splice_routed: the image-feature rows [glob | sep | routed] are never materialised, the row's source is resolved from the
+// router's device arrays, and it takes the two roundings of the per-image path's tokens.to(images.dtype) -> splice cast.
+//   src <= -2: q = -2 - src, image b = q >> 32, position p = q & 0xffffffff:
+//   p < P global token row local_row_off[b] - P + p; p == P table row sep_id; p > P token row local_row_off[b] + keep_idx[b, p - P - 1].
+__device__ __forceinline__ SpliceRow splice_resolve_routed(long long s, const void* table, int table_dtype, long table_rows, long sep_id,
+                                                           const float* tokens, long token_rows, const long long* local_row_off,
+                                                           const int* n_rows, int B, int P, int T_max, const int* keep_idx,
+                                                           const int* keep_count) {
     long long trow = -1, krow = -1;                       // table row / token row of this output row; both -1: zeros
     if (s >= 0) {
         if (s < table_rows) trow = s;
@@ -134,42 +165,77 @@ __global__ void __launch_bounds__(256) splice_routed_kernel(const void* table, i
             if (krow >= token_rows) krow = -1;
         }
     }
-    if (trow < 0 && krow < 0) {
-        for (int c = lane * 16; c < H * es_out; c += 1024) *reinterpret_cast<u32x4*>(o + c) = u32x4{0u, 0u, 0u, 0u};
-        return;
+    // a table row named by an image position is the separator: it takes the image features' two roundings
+    return krow >= 0 ? SpliceRow::token(tokens, krow) : trow >= 0 ? SpliceRow::typed(table, table_dtype, trow, s <= -2) : SpliceRow::zero();
+}
+__global__ void __launch_bounds__(256) splice_routed_kernel(const void* table, int table_dtype, long table_rows, long sep_id,
+                                                            const float* tokens, long token_rows, const long long* local_row_off,
+                                                            const int* n_rows, int B, int P, int T_max, const int* keep_idx,
+                                                            const int* keep_count, int mid_dtype, const long long* src, void* out,
+                                                            int out_dtype, long rows, int H) {
+    const long r = splice_wave_row();
+    if (r >= rows) return;
+    splice_emit(splice_resolve_routed(src[r], table, table_dtype, table_rows, sep_id, tokens, token_rows, local_row_off, n_rows, B, P, T_max,
+                                      keep_idx, keep_count), mid_dtype, out, out_dtype, r, H);
+}
+
+// slime_splice_merged, the un-sampled LLaVA-NeXT merge ('spatial' / 'spatial_unpad'): the merged per-image features are never
+// materialised, the host plan names every output row's source directly.
+//   src <= -2: row k = -2 - src of [tokens | extra]: k < token_rows row k of the fp32 projector output through the two roundings
+//   fp32 -> mid -> out; token_rows <= k < token_rows + extra_rows row k - token_rows of `extra` (model.image_newline), one cast or
+//   a bit copy, no middle rounding.
+__device__ __forceinline__ SpliceRow splice_resolve_merged(long long s, const void* table, int table_dtype, long table_rows,
+                                                           const float* tokens, long token_rows, const void* extra, int extra_dtype,
+                                                           long extra_rows) {
+    long long krow = -1, crow = -1;                       // fp32 token row / row of a typed tensor (table or extra); both -1: zeros
+    const void* cbase = table;
+    int cdt = table_dtype;
+    if (s >= 0) {
+        if (s < table_rows) crow = s;
+    } else if (s <= -2) {
+        const long long k = -2 - s;                       // s >= INT64_MIN, so k <= INT64_MAX - 1: no overflow
+        if (k < token_rows) krow = k;
+        else if (k - token_rows < extra_rows) { crow = k - token_rows; cbase = extra; cdt = extra_dtype; }
     }
-    if (krow >= 0) {                                      // image token: fp32 -> mid -> out
-        const float* t = tokens + (size_t)krow * H;
-        if (out_dtype == SLIME_F32) {
-            for (int c = lane * 4; c < H; c += 256) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(t + c);
-                *reinterpret_cast<f32x4*>(o + (size_t)c * 4) = f32x4{round_through(v[0], mid_dtype), round_through(v[1], mid_dtype),
-                                                                      round_through(v[2], mid_dtype), round_through(v[3], mid_dtype)};
-            }
-            return;
-        }
-        for (int c = lane * 8; c < H; c += 512) {
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(t + c), v1 = *reinterpret_cast<const f32x4*>(t + c + 4);
-            u32x4 w;
-            w[0] = pack2_as(round_through(v0[0], mid_dtype), round_through(v0[1], mid_dtype), out_dtype);
-            w[1] = pack2_as(round_through(v0[2], mid_dtype), round_through(v0[3], mid_dtype), out_dtype);
-            w[2] = pack2_as(round_through(v1[0], mid_dtype), round_through(v1[1], mid_dtype), out_dtype);
-            w[3] = pack2_as(round_through(v1[2], mid_dtype), round_through(v1[3], mid_dtype), out_dtype);
-            *reinterpret_cast<u32x4*>(o + (size_t)c * 2) = w;
-        }
-        return;
-    }
-    if (s <= -2) {                                        // separator: a table row that takes the image features' two roundings
-        for (int c = lane; c < H; c += 64)
-            store_from_float(out, out_dtype, (size_t)r * H + c, round_through(load_as_float(table, table_dtype, (size_t)trow * H + c), mid_dtype));
-        return;
-    }
-    if (table_dtype == out_dtype) {                       // text token: splice_rows' rule
-        const char* p = reinterpret_cast<const char*>(table) + (size_t)trow * H * es_out;
-        for (int c = lane * 16; c < H * es_out; c += 1024) *reinterpret_cast<u32x4*>(o + c) = *reinterpret_cast<const u32x4*>(p + c);
-        return;
-    }
-    for (int c = lane; c < H; c += 64) store_from_float(out, out_dtype, (size_t)r * H + c, load_as_float(table, table_dtype, (size_t)trow * H + c));
+    return krow >= 0 ? SpliceRow::token(tokens, krow) : crow >= 0 ? SpliceRow::typed(cbase, cdt, crow) : SpliceRow::zero();
+}
+__global__ void __launch_bounds__(256) splice_merged_kernel(const void* table, int table_dtype, long table_rows, const float* tokens,
+                                                            long token_rows, int mid_dtype, const void* extra, int extra_dtype,
+                                                            long extra_rows, const long long* src, void* out, int out_dtype, long rows,
+                                                            int H) {
+    const long r = splice_wave_row();
+    if (r >= rows) return;
+    splice_emit(splice_resolve_merged(src[r], table, table_dtype, table_rows, tokens, token_rows, extra, extra_dtype, extra_rows), mid_dtype,
+                out, out_dtype, r, H);
+}
+
+// The checks the three entries share, under the entry's name and in its own words for what must be a multiple of 16 bytes and
+// what must be aligned (`ptrs`: the OR of the pointers).  A 16-bit row of whole 16-byte pieces is a multiple of 8 elements, so the
+// fp32 token rows are whole pieces too.  The texts that result:
+//   splice_rows: rows must be multiples of 16 bytes (H=%d)             splice_rows: pointers must be 16-byte aligned
+//   splice_routed / splice_merged: fp32 token rows and output rows must be multiples of 16 bytes (H=%d)
+//   splice_routed: out, table and tokens must be 16-byte aligned       splice_merged: out, table, tokens and extra must be 16-byte aligned
+static bool splice_dtype_ok(int dt) { return dt == SLIME_F32 || dt == SLIME_BF16 || dt == SLIME_F16; }
+static int splice_check_layout(const char* entry, const char* rows_what, const char* ptrs_what, int out_dtype, int H, uintptr_t ptrs) {
+    SLIME_REQUIRE((H * (out_dtype == SLIME_F32 ? 4 : 2)) % 16 == 0, "%s: %s must be multiples of 16 bytes (H=%d)", entry, rows_what, H);
+    SLIME_REQUIRE(ptrs % 16 == 0, "%s: %s must be 16-byte aligned", entry, ptrs_what);
+    return SLIME_OK;
+}
+
+extern "C" int slime_splice_rows(const void* table, int table_dtype, long table_rows, const void* feats, int feats_dtype,
+                                 long feat_rows, const int64_t* src, void* out, int out_dtype, long rows, int H, void* stream) {
+    SLIME_REQUIRE(src && out && rows > 0 && H > 0, "splice_rows: bad input");
+    SLIME_REQUIRE(table || feats, "splice_rows: neither an embedding table nor image features");
+    SLIME_REQUIRE(table_rows >= 0 && feat_rows >= 0, "splice_rows: negative source size");
+    SLIME_REQUIRE(splice_dtype_ok(out_dtype) && (!table || splice_dtype_ok(table_dtype)) && (!feats || splice_dtype_ok(feats_dtype)),
+                  "splice_rows: bad dtype");
+    if (int rc = splice_check_layout("splice_rows", "rows", "pointers", out_dtype, H, (uintptr_t)out | (uintptr_t)table | (uintptr_t)feats))
+        return rc;
+    hipLaunchKernelGGL(splice_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, table, table_dtype,
+                       feats, feats_dtype, reinterpret_cast<const long long*>(src), out, out_dtype, rows, H,
+                       table ? table_rows : 0, feats ? feat_rows : 0);
+    SLIME_CHECK_LAUNCH("splice_rows");
+    return SLIME_OK;
 }
 
 extern "C" int slime_splice_routed(const void* table, int table_dtype, long table_rows, long sep_id, const float* tokens,
@@ -182,78 +248,16 @@ extern "C" int slime_splice_routed(const void* table, int table_dtype, long tabl
                   rows, H, B, T_max, P);
     SLIME_REQUIRE(token_rows >= 0, "splice_routed: token_rows=%ld is negative", token_rows);
     SLIME_REQUIRE(sep_id >= 0 && sep_id < table_rows, "splice_routed: sep_id=%ld outside the table's %ld rows", sep_id, table_rows);
-    auto ok = [](int dt) { return dt == SLIME_F32 || dt == SLIME_BF16 || dt == SLIME_F16; };
-    SLIME_REQUIRE(ok(table_dtype) && ok(mid_dtype) && ok(out_dtype), "splice_routed: bad dtype (table %d, mid %d, out %d: F32, BF16 or F16)",
-                  table_dtype, mid_dtype, out_dtype);
-    SLIME_REQUIRE((H * (out_dtype == SLIME_F32 ? 4 : 2)) % 16 == 0 && (H * 4) % 16 == 0,
-                  "splice_routed: fp32 token rows and output rows must be multiples of 16 bytes (H=%d)", H);
-    SLIME_REQUIRE(((uintptr_t)out % 16) == 0 && ((uintptr_t)table % 16) == 0 && ((uintptr_t)tokens % 16) == 0,
-                  "splice_routed: out, table and tokens must be 16-byte aligned");
+    SLIME_REQUIRE(splice_dtype_ok(table_dtype) && splice_dtype_ok(mid_dtype) && splice_dtype_ok(out_dtype),
+                  "splice_routed: bad dtype (table %d, mid %d, out %d: F32, BF16 or F16)", table_dtype, mid_dtype, out_dtype);
+    if (int rc = splice_check_layout("splice_routed", "fp32 token rows and output rows", "out, table and tokens", out_dtype, H,
+                                     (uintptr_t)out | (uintptr_t)table | (uintptr_t)tokens))
+        return rc;
     hipLaunchKernelGGL(splice_routed_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, table, table_dtype,
                        table_rows, sep_id, tokens, token_rows, local_row_off, n_rows, B, P, T_max, keep_idx, keep_count, mid_dtype,
                        reinterpret_cast<const long long*>(src), out, out_dtype, rows, H);
     SLIME_CHECK_LAUNCH("splice_routed");
     return SLIME_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ merged splice
-// One wave per output row, as the two kernels above, for the un-sampled LLaVA-NeXT merge ('spatial' / 'spatial_unpad'): the merged
-// per-image features are never materialised, the host plan names every output row's source directly.
-//   src >= 0: table row (splice_rows' rule); src == -1: zeros; src <= -2: k = -2 - src: k < token_rows row k of the fp32 projector
-//   output through the two roundings fp32 -> mid -> out (16 B per lane in and out); token_rows <= k < token_rows + extra_rows row
-//   k - token_rows of `extra` (model.image_newline), one cast or a bit copy, no middle rounding.
-// A source that resolves outside its tensor is never dereferenced: the row is zeroed.
-__global__ void __launch_bounds__(256) splice_merged_kernel(const void* table, int table_dtype, long table_rows, const float* tokens,
-                                                            long token_rows, int mid_dtype, const void* extra, int extra_dtype,
-                                                            long extra_rows, const long long* src, void* out, int out_dtype, long rows,
-                                                            int H) {
-    const int lane = threadIdx.x & 63;
-    const long r = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (r >= rows) return;
-    const long long s = src[r];
-    const int es_out = out_dtype == SLIME_F32 ? 4 : 2;
-    char* o = reinterpret_cast<char*>(out) + (size_t)r * H * es_out;
-    long long krow = -1, crow = -1;                       // fp32 token row / row of a typed tensor (table or extra); both -1: zeros
-    const void* cbase = table;
-    int cdt = table_dtype;
-    if (s >= 0) {
-        if (s < table_rows) crow = s;
-    } else if (s <= -2) {
-        const long long k = -2 - s;                       // s >= INT64_MIN, so k <= INT64_MAX - 1: no overflow
-        if (k < token_rows) krow = k;
-        else if (k - token_rows < extra_rows) { crow = k - token_rows; cbase = extra; cdt = extra_dtype; }
-    }
-    if (krow < 0 && crow < 0) {
-        for (int c = lane * 16; c < H * es_out; c += 1024) *reinterpret_cast<u32x4*>(o + c) = u32x4{0u, 0u, 0u, 0u};
-        return;
-    }
-    if (krow >= 0) {                                      // image token: fp32 -> mid -> out
-        const float* t = tokens + (size_t)krow * H;
-        if (out_dtype == SLIME_F32) {
-            for (int c = lane * 4; c < H; c += 256) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(t + c);
-                *reinterpret_cast<f32x4*>(o + (size_t)c * 4) = f32x4{round_through(v[0], mid_dtype), round_through(v[1], mid_dtype),
-                                                                      round_through(v[2], mid_dtype), round_through(v[3], mid_dtype)};
-            }
-            return;
-        }
-        for (int c = lane * 8; c < H; c += 512) {         // a 16-bit output row of whole 16-byte pieces: H is a multiple of 8
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(t + c), v1 = *reinterpret_cast<const f32x4*>(t + c + 4);
-            u32x4 w;
-            w[0] = pack2_as(round_through(v0[0], mid_dtype), round_through(v0[1], mid_dtype), out_dtype);
-            w[1] = pack2_as(round_through(v0[2], mid_dtype), round_through(v0[3], mid_dtype), out_dtype);
-            w[2] = pack2_as(round_through(v1[0], mid_dtype), round_through(v1[1], mid_dtype), out_dtype);
-            w[3] = pack2_as(round_through(v1[2], mid_dtype), round_through(v1[3], mid_dtype), out_dtype);
-            *reinterpret_cast<u32x4*>(o + (size_t)c * 2) = w;
-        }
-        return;
-    }
-    if (cdt == out_dtype) {                               // text token / newline row of the output's type: bit copy
-        const char* p = reinterpret_cast<const char*>(cbase) + (size_t)crow * H * es_out;
-        for (int c = lane * 16; c < H * es_out; c += 1024) *reinterpret_cast<u32x4*>(o + c) = *reinterpret_cast<const u32x4*>(p + c);
-        return;
-    }
-    for (int c = lane; c < H; c += 64) store_from_float(out, out_dtype, (size_t)r * H + c, load_as_float(cbase, cdt, (size_t)crow * H + c));
 }
 
 extern "C" int slime_splice_merged(const void* table, int table_dtype, long table_rows, const float* tokens, long token_rows,
@@ -265,14 +269,12 @@ extern "C" int slime_splice_merged(const void* table, int table_dtype, long tabl
                   "splice_merged: table_rows=%ld token_rows=%ld extra_rows=%ld must not be negative", table_rows, token_rows, extra_rows);
     SLIME_REQUIRE((tokens != nullptr) == (token_rows != 0), "splice_merged: tokens may be null exactly when token_rows=%ld is 0", token_rows);
     SLIME_REQUIRE((extra != nullptr) == (extra_rows != 0), "splice_merged: extra may be null exactly when extra_rows=%ld is 0", extra_rows);
-    auto ok = [](int dt) { return dt == SLIME_F32 || dt == SLIME_BF16 || dt == SLIME_F16; };
-    SLIME_REQUIRE(ok(table_dtype) && ok(mid_dtype) && ok(out_dtype) && (!extra || ok(extra_dtype)),
+    SLIME_REQUIRE(splice_dtype_ok(table_dtype) && splice_dtype_ok(mid_dtype) && splice_dtype_ok(out_dtype) && (!extra || splice_dtype_ok(extra_dtype)),
                   "splice_merged: bad dtype (table %d, mid %d, extra %d, out %d: F32, BF16 or F16)", table_dtype, mid_dtype, extra_dtype,
                   out_dtype);
-    SLIME_REQUIRE((H * (out_dtype == SLIME_F32 ? 4 : 2)) % 16 == 0 && (H * 4) % 16 == 0,
-                  "splice_merged: fp32 token rows and output rows must be multiples of 16 bytes (H=%d)", H);
-    SLIME_REQUIRE(((uintptr_t)out % 16) == 0 && ((uintptr_t)table % 16) == 0 && ((uintptr_t)tokens % 16) == 0 && ((uintptr_t)extra % 16) == 0,
-                  "splice_merged: out, table, tokens and extra must be 16-byte aligned");
+    if (int rc = splice_check_layout("splice_merged", "fp32 token rows and output rows", "out, table, tokens and extra", out_dtype, H,
+                                     (uintptr_t)out | (uintptr_t)table | (uintptr_t)tokens | (uintptr_t)extra))
+        return rc;
     hipLaunchKernelGGL(splice_merged_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, table, table_dtype,
                        table_rows, tokens, token_rows, mid_dtype, extra, extra_dtype, extra_rows, reinterpret_cast<const long long*>(src),
                        out, out_dtype, rows, H);
@@ -568,6 +570,16 @@ extern "C" void slime_prefill_set_debug(void* counters) { g_prefill_dbg = (unsig
 static constexpr int g_prefill_variant = 0;
 #endif
 
+// One launch of a prefill kernel, all of which need more than 64 KiB of LDS.  The kernel is a template ARGUMENT, not a function
+// argument: the opt-in's function-local static is then one per kernel instantiation (the kernels share one function type).
+template <void (*KERN)(PrefillArgs)>
+static int prefill_launch(dim3 grid, dim3 block, int lds, hipStream_t s, const PrefillArgs& a) {
+    SLIME_SET_LDS_ONCE(KERN, lds, "prefill_attention");
+    hipLaunchKernelGGL(KERN, grid, block, lds, s, a);
+    SLIME_CHECK_LAUNCH("prefill_attention");
+    return SLIME_OK;
+}
+
 // One implementation behind slime_prefill_attention (window 0) and slime_prefill_attention_window.  window == 0 or >= S: the
 // unwindowed kernels, the very launches of the existing entry.  0 < window < S: the WIN instantiation of the kernel the unwindowed
 // call would take -- prefill32_kernel for group 4 / bf16, the eight-wave kernel otherwise (and for diagnostic variant 1).
@@ -603,52 +615,23 @@ static int prefill_attention_run(const void* q, long q_bs, long q_rs, const void
         SLIME_REQUIRE(items < (1L << 30), "prefill_attention: sequence too long");
         const int cus = num_cus() >= 8 ? (num_cus() & ~7) : 8;      // (a multiple of 8: the snake's mirror stays inside an XCD class)
         const int grid = (g_prefill_variant == 2 || items <= cus) ? (int)items : cus;
+        const dim3 g32(grid), b32(256);
 #ifdef SLIME_DIAG
-        if (g_prefill_variant == 3 && !win) {                    // look-ahead of 4 key steps instead of 6 (unwindowed calls only)
-            auto kern4 = prefill32_kernel<BF16, 4>;
-            SLIME_SET_LDS_ONCE(kern4, LDS32, "prefill_attention");
-            hipLaunchKernelGGL(kern4, dim3(grid), dim3(256), LDS32, s, a);
-            SLIME_CHECK_LAUNCH("prefill_attention");
-            return SLIME_OK;
-        }
+        if (g_prefill_variant == 3 && !win)                      // look-ahead of 4 key steps instead of 6 (unwindowed calls only)
+            return prefill_launch<prefill32_kernel<BF16, 4>>(g32, b32, LDS32, s, a);
 #endif
-        if (win) {
-            auto kern = prefill32_kernel<BF16, 6, true>;
-            SLIME_SET_LDS_ONCE(kern, LDS32, "prefill_attention");
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDS32, s, a);
-        } else {
-            auto kern = prefill32_kernel<BF16>;
-            SLIME_SET_LDS_ONCE(kern, LDS32, "prefill_attention");
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDS32, s, a);
-        }
-        SLIME_CHECK_LAUNCH("prefill_attention");
-        return SLIME_OK;
+        return win ? prefill_launch<prefill32_kernel<BF16, 6, true>>(g32, b32, LDS32, s, a) : prefill_launch<prefill32_kernel<BF16>>(g32, b32, LDS32, s, a);
     }
     constexpr int LDS = 2 * 192 * 256;
     const int QB = 256 / group, nqb = (S + QB - 1) / QB;
     SLIME_REQUIRE(nqb <= 65535, "prefill_attention: sequence too long");
-    if (win && dtype == SLIME_F16) {
-        auto kern = prefill_attn_kernel<F16, true>;
-        SLIME_SET_LDS_ONCE(kern, LDS, "prefill_attention");
-        hipLaunchKernelGGL(kern, dim3(n_kv_heads, batch, nqb), dim3(512), LDS, s, a);
-    } else if (win && dtype == SLIME_BF16) {
-        auto kern = prefill_attn_kernel<BF16, true>;
-        SLIME_SET_LDS_ONCE(kern, LDS, "prefill_attention");
-        hipLaunchKernelGGL(kern, dim3(n_kv_heads, batch, nqb), dim3(512), LDS, s, a);
-    } else if (dtype == SLIME_F16) {
-        auto kern = prefill_attn_kernel<F16>;
-        SLIME_SET_LDS_ONCE(kern, LDS, "prefill_attention");
-        hipLaunchKernelGGL(kern, dim3(n_kv_heads, batch, nqb), dim3(512), LDS, s, a);
-    } else if (dtype == SLIME_BF16) {
-        auto kern = prefill_attn_kernel<BF16>;
-        SLIME_SET_LDS_ONCE(kern, LDS, "prefill_attention");
-        hipLaunchKernelGGL(kern, dim3(n_kv_heads, batch, nqb), dim3(512), LDS, s, a);
-    } else {
-        slime_set_error("prefill_attention: dtype %d is not a 16-bit MFMA type", dtype);
-        return SLIME_EINVAL;
-    }
-    SLIME_CHECK_LAUNCH("prefill_attention");
-    return SLIME_OK;
+    const dim3 g8(n_kv_heads, batch, nqb), b8(512);
+    if (dtype == SLIME_F16)
+        return win ? prefill_launch<prefill_attn_kernel<F16, true>>(g8, b8, LDS, s, a) : prefill_launch<prefill_attn_kernel<F16>>(g8, b8, LDS, s, a);
+    if (dtype == SLIME_BF16)
+        return win ? prefill_launch<prefill_attn_kernel<BF16, true>>(g8, b8, LDS, s, a) : prefill_launch<prefill_attn_kernel<BF16>>(g8, b8, LDS, s, a);
+    slime_set_error("prefill_attention: dtype %d is not a 16-bit MFMA type", dtype);
+    return SLIME_EINVAL;
 }
 
 extern "C" int slime_prefill_attention(const void* q, long q_bs, long q_rs, const void* k, long k_bs, long k_rs, const void* v,

@@ -48,6 +48,63 @@ def test_splice_kernel_bit_exact_vs_reference(dev, name, dtype):
     assert torch.equal(mixed.cpu(), c["out_embeds"].to(torch.bfloat16))
 
 
+def _splice_rows_call(dev, table_d, table_rows, feats_d, feat_rows, src, out, H):
+    """slime_splice_rows on a buffer with 4 sentinel rows in front of and behind the rows it may write."""
+    from slime_amd import _lib, ops
+    from test_gpu_splice_routed import SENTINEL
+    src_d = src.to(dev)
+    buf = torch.full((src.numel() + 8, H), SENTINEL, dtype=out, device=dev)
+    _lib.check(_lib.load().slime_splice_rows(None if table_d is None else table_d.data_ptr(), 0 if table_d is None else ops.dtype_code(table_d.dtype),
+                                             table_rows, None if feats_d is None else feats_d.data_ptr(),
+                                             0 if feats_d is None else ops.dtype_code(feats_d.dtype), feat_rows, src_d.data_ptr(),
+                                             buf[4:].data_ptr(), ops.dtype_code(out), src.numel(), H, torch.cuda.current_stream().cuda_stream),
+               "slime_splice_rows")
+    got = buf.cpu()
+    assert bool((got[:4] == SENTINEL).all()) and bool((got[-4:] == SENTINEL).all()), "rows outside [0, rows) were written"
+    return got[4:-4]
+
+
+@pytest.mark.parametrize("out_dt", ["f32", "bf16", "f16"])
+@pytest.mark.parametrize("feats_dt", ["f32", "bf16", "f16"])
+@pytest.mark.parametrize("table_dt", ["f32", "bf16", "f16"])
+@pytest.mark.parametrize("H", [8, 264])
+def test_splice_rows_dtype_matrix_bit_for_bit(dev, H, table_dt, feats_dt, out_dt):
+    """Every (table, feats, out) type through the C entry: out[r] carries the bits of table[i].to(out) / feats[k].to(out) on the CPU
+    (equal types: the source's own bits).  H = 8: the smallest legal 16-bit row, one 16-byte piece; H = 264: an 8-byte tail in the
+    16-byte sweep of a 16-bit row and a partial 64-lane sweep of the cast loop.  The call is told one row fewer than each tensor
+    holds, so the id equal to table_rows and the feature index equal to feat_rows -- both to be zeroed -- would read valid memory
+    in a kernel without the guards."""
+    from slime_amd import ops
+    from test_gpu_splice_routed import DT, assert_same_bits, bits, data
+    tokens32, table32 = data(H)
+    table32 = table32.clone()
+    table32[3], table32[12] = tokens32[0], tokens32[2]          # text rows 3 and 12 carry the ties, subnormals and overflows too
+    table, feats, out = table32.to(DT[table_dt]), tokens32.to(DT[feats_dt]), DT[out_dt]
+    nt, nf = table.shape[0] - 1, feats.shape[0] - 1
+    assert float(table[nt].float().abs().sum()) > 0 and float(feats[nf].float().abs().sum()) > 0     # a zero row means "not read"
+    ids = [3, 0, nt - 1, -2 - (nf - 1), -2 - 0, -1, -2 - 7, nt, -2 - nf, 12, -2 - 13, -1, nt - 1, -2 - 2]
+    assert len(ids) % 4 != 0 and len(ids) > 8
+    src = torch.tensor(ids, dtype=torch.int64)
+    want = torch.zeros(len(ids), H, dtype=out)
+    for r, s in enumerate(ids):
+        if 0 <= s < nt:
+            want[r] = table[s].to(out)
+        elif s <= -2 and -2 - s < nf:
+            want[r] = feats[-2 - s].to(out)
+    table_d, feats_d = table.to(dev), feats.to(dev)
+    got = _splice_rows_call(dev, table_d, nt, feats_d, nf, src, out, H)
+    assert_same_bits(got, want)
+    for r in (5, 7, 8, 11):
+        assert bool((bits(got[r]) == 0).all()), f"row {r} (src {ids[r]}) is not a zero row"
+    if (H, table_dt, feats_dt, out_dt) == (264, "bf16", "f32", "f16"):           # the wrapper makes the same call
+        assert_same_bits(ops.splice_rows(table_d[:nt], feats_d[:nf], src.to(dev), out).cpu(), want, "ops.splice_rows")
+    # a source tensor that is absent: its rows are zero rows, whatever size the call states for it
+    got = _splice_rows_call(dev, None, nt, feats_d, nf, src, out, H)
+    assert_same_bits(got, torch.where((src >= 0).unsqueeze(1), torch.zeros_like(want), want), "table=None")
+    got = _splice_rows_call(dev, table_d, nt, None, nf, src, out, H)
+    assert_same_bits(got, torch.where((src <= -2).unsqueeze(1), torch.zeros_like(want), want), "feats=None")
+
+
 def test_prepare_inputs_labels_for_multimodal_end_to_end(dev):
     """The reference-shaped method on the tiny encoder: encode_images (HIP tower + adapter + router) feeds the splice;
     checked against the oracle's splice of the very same visual tokens, and the None-passing contract of :456-470."""
